@@ -5,7 +5,12 @@ One "step" = one chunk of the stream = evict (sink/window) -> ViT on the chunk's
 LLM prefill of the chunk's ~275 new tokens -> 20 greedy decode tokens, through
 ``streaming_inference`` with its inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 2b|7b|tiny]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 2b|7b|tiny] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the benchmark measures, each
+its own pass after the timed one: the strict-causal / PCIe-inclusive / EOS-polling passes, the per-kernel roofline pass (and
+configs[4]'s prefill rooflines), and the CPU oracle baseline (`--no-extra-values` / `--no-roofline` / `--no-cpu-baseline` drop
+one of them again).  `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 
 N > 1: one independent stream per rank, RCCL barrier only around the timed region (streams never
 interact -> "weak" scaling).  Launched by the driver with torch.distributed.run (RANK / WORLD_SIZE / MASTER_* in
@@ -89,9 +94,14 @@ def main():
     ap.add_argument("--prefill-chunks", type=int, default=300, help="dense_prefill: chunks piled into the opening forward (300 = 5 min)")
     ap.add_argument("--vit-fp8", action="store_true", help="vision tower Linears on the fp8 MFMA path (svlm_gemm_fp8; configs[4])")
     ap.add_argument("--decode-tail", action="store_true", help="decode step on the persistent layer-tail kernel (svlm_dec_tail) instead of the per-op launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra-values", action="store_true", help="skip the strict-causal / PCIe-inclusive / EOS-polling passes behind the contract's run")
+    ap.add_argument("--full", action="store_true", help="after the contract's timed run, also the extra passes, the roofline pass and the CPU "
+                                                        "baseline (each its own run; off by default: a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its tokens, the last forward's logits, a fixed sample of the KV cache) "
+                         "as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
+    ap.add_argument("--no-extra-values", action="store_true", help="with --full: skip the strict-causal / PCIe-inclusive / EOS-polling passes behind the contract's run")
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=None,
                     help="BASELINE.json configs[n]: 1 = the default line (2B, 1 fps, window 2048); 2 = 7B, 2 fps, window 4096; 3 = config 2 as "
                          "N independent streams (use with --gpus 8); 4 = config 2's model opened by the 5-minute dense prefill")
@@ -103,6 +113,8 @@ def main():
             setattr(args, k, v)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))            # before anything touches a GPU
@@ -179,6 +191,7 @@ def main():
         MS.fence(dist, dev)
 
     stamps = []
+    dumped = {}          # --dump-outputs: host copies of the last timed chunk's results (capture_outputs)
 
     # the host side of the loop is a few hundred microseconds of single-threaded Python per chunk; torch's CPU thread pool (one thread per
     # core: 256 on these boxes, behind a 16-CPU quota) has nothing to do here and must not wake up for a stray CPU tensor op
@@ -238,6 +251,8 @@ def main():
         if i == first_timed + args.steps:
             fence()
             t["t1"] = time.perf_counter()
+            if args.dump_outputs and rank == 0:          # the last timed chunk's results, before the trailing chunk touches them
+                dumped.update(capture_outputs(model._svlm_engine, counts[-1]))
 
     S.streaming_inference(model=model, processor=proc, video=video, model_base="Qwen2_5" if cfg.family == "qwen2_5" else "Qwen2",
                           duration=n_chunks, previous_text="",
@@ -302,7 +317,7 @@ def main():
     # on the same engine): strict-causal (no look-ahead ViT: chunk i+1's frames are not touched before chunk i is answered),
     # PCIe-inclusive (uint8 frames from pinned host memory, H2D + patchify inside the timed region), and with EOS live (tokens polled
     # every 4th step, the path every real captioning run takes; random weights almost never emit EOS, so the token count is the same)
-    if world == 1 and not dense and not args.no_extra_values:
+    if args.full and world == 1 and not dense and not args.no_extra_values:
         def extra_pass(lookahead=True, ingest=args.ingest, suppress_eos=True):
             n2 = fill + 3 + args.steps + 1
             first2 = fill + 3
@@ -330,19 +345,58 @@ def main():
         if args.ingest != "host":
             out["value_ingest_host"], _ = extra_pass(ingest="host")
         out["value_eos_polling"], out["decode_tokens_per_sec_eos_polling"] = extra_pass(suppress_eos=False)
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         log("roofline pass (eager launches bracketed by HIP events)")
         out.update(roofline_pass(model, args, kv_steady[0]))
-    if rank == 0 and dense:
+    if args.full and rank == 0 and dense:
         out.update(dense_prefill_rooflines(model, out["dense_prefill"]["prompt_rows"]))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dense:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dense:
         log("cpu baseline (oracle on host cores)")
         out["cpu_baseline"] = cpu_baseline(cfg, sd, args)
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, dumped)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+KV_SAMPLE_ROWS = 96          # seeded logical rows of the cache in the dump, plus its last KV_TAIL_ROWS rows
+KV_TAIL_ROWS = 32
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def capture_outputs(eng, n_new):
+    """What the chunk that just finished handed its caller, copied to the host (called between two chunks, device idle):
+    the generated tokens (`.sequences` tail), the last forward's fp32 logits (what `keep_logits` returns last) and a fixed
+    sample of `past_key_values`: rows in logical order, every layer / K and V / kv head, as the cache's (1, Hkv, L, D) views
+    hold them.  The sample rows are KV_SAMPLE_ROWS drawn with a fixed seed from [0, L) plus the last KV_TAIL_ROWS rows."""
+    import numpy as np
+    cache = eng._last_cache
+    L = int(cache.length)
+    rng = np.random.default_rng(0)
+    rows = np.union1d(rng.choice(L, min(KV_SAMPLE_ROWS, L), replace=False), np.arange(max(0, L - KV_TAIL_ROWS), L))
+    slots = torch.from_numpy(cache.slot_of[rows].astype(np.int64)).to(cache.pool.device)
+    return {"tokens": eng.tok_buf[:n_new].cpu().numpy().astype(np.float64),
+            "logits": eng.logits.detach().cpu().numpy().astype(np.float32),
+            "kv_sample": cache.pool.index_select(3, slots).float().cpu().numpy(),          # (layers, K|V, Hkv, rows, D)
+            "kv_sample_rows": rows.astype(np.float64),
+            "kv_len": np.array([L], dtype=np.float64)}
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every captured array (float32 / float64); returns {name: shape}."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if not arrays or total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {len(arrays)} arrays, {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def dense_prefill_rooflines(model, prompt_rows):
