@@ -292,6 +292,33 @@ int svlm_dec_lm_head_sample(const void* x, const void* ln_w, float eps, const vo
                             float penalty, const int* suppress, int n_suppress, void* ws, int V, int K, float temperature,
                             const unsigned* rng, const int* state, void* stream);
 
+/* ---- opt-in fp8 language-model weights (csrc/decode_fp8.hip; SvlmEngine(llm_fp8=True)).  W8 is OCP e4m3 (float8_e4m3fn), one fp32
+ * scale per output row (w_scale[n], a power of two: weights.py:quantize_rows_fp8_pow2), W' = W8 * w_scale exact in bf16.  Each entry
+ * is its bf16 twin with W8 + w_scale in place of W: same prologue, epilogue and rounding points, the scale applied once per row in the
+ * epilogue, so each computes the bf16 entry on W' up to the fp32 summation order.  K and ldw: multiples of 16 (one 16-B load = 16
+ * weights).
+ * replaces: qwen2/language_forward.py:183,80-82 + generate/streaming_cache.py:72-73 (as svlm_dec_qkv_lin). */
+int svlm_dec_qkv_fp8(const void* x, const void* ln_w, float eps, const void* W8, int ldw, const float* w_scale, const void* bias,
+                     void* q_out, void* k_planes, void* v_planes, const int* slot_of, const int* len_dev, int len_host, int K, int qd,
+                     int kd, int D, int n_slots, void* k_lin, void* v_lin, int lin_rows, void* stream);
+/* replaces: qwen2/language_forward.py:200-201 (Qwen2MLP gate/up + SwiGLU, as svlm_dec_gate_up). */
+int svlm_dec_gate_up_fp8(const void* x, const void* ln_w, float eps, const void* W8, int ldw, const float* w_scale, void* h, int I, int K,
+                         void* stream);
+/* y = bf16(W' x + bias) (+ residual, rounded again), y_f32 = the same value in fp32; act must be 0 (none).
+ * replaces: o_proj / down_proj at T = 1 (qwen2/language_forward.py:161,201) and the last-row lm_head (qwen2/model_forward.py:243). */
+int svlm_gemv_fp8(const void* x, const void* W8, int ldw, const float* w_scale, const void* bias, const void* residual, void* y,
+                  float* y_f32, int N, int K, int act, void* stream);
+/* svlm_dec_lm_head / svlm_dec_lm_head_sample on W8: same candidates in ws (svlm_dec_lm_head_ws_bytes), completed by svlm_argmax_finish.
+ * replaces: qwen2/language_forward.py:315, qwen2/model_forward.py:243, generate/streaming_generate_qwen.py:73-104. */
+int svlm_dec_lm_head_fp8(const void* x, const void* ln_w, float eps, const void* W8, int ldw, const float* w_scale, float* logits,
+                         const void* seen, float penalty, const int* suppress, int n_suppress, void* ws, int V, int K, void* stream);
+int svlm_dec_lm_head_sample_fp8(const void* x, const void* ln_w, float eps, const void* W8, int ldw, const float* w_scale, float* logits,
+                                const void* seen, float penalty, const int* suppress, int n_suppress, void* ws, int V, int K,
+                                float temperature, const unsigned* rng, const int* state, void* stream);
+/* dst[r, c] = bf16(src8[r, c] * scale[r]) for contiguous [rows, cols] matrices (cols a multiple of 16): the bf16 image W' of one layer,
+ * which the prefill GEMMs read.  replaces: nothing (the reference has bf16 weights; this rebuilds them from the fp8 copy). */
+int svlm_dequant_fp8_bf16(const void* src8, const float* scale, void* dst, int rows, int cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,12 @@ SIGNATURES = {
     "svlm_dec_lm_head_ws_bytes": (_ll, [_i]),
     "svlm_dec_lm_head": (_i, [_p, _p, _f, _p, _i, _p, _p, _f, _p, _i, _p, _i, _i, _p]),
     "svlm_argmax_finish": (_i, [_p, _i, _p, _p, _p, _i, _p]),
+    "svlm_dec_qkv_fp8": (_i, [_p, _p, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "svlm_dec_gate_up_fp8": (_i, [_p, _p, _f, _p, _i, _p, _p, _i, _i, _p]),
+    "svlm_gemv_fp8": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "svlm_dec_lm_head_fp8": (_i, [_p, _p, _f, _p, _i, _p, _p, _p, _f, _p, _i, _p, _i, _i, _p]),
+    "svlm_dec_lm_head_sample_fp8": (_i, [_p, _p, _f, _p, _i, _p, _p, _p, _f, _p, _i, _p, _i, _i, _f, _p, _p, _p]),
+    "svlm_dequant_fp8_bf16": (_i, [_p, _p, _p, _i, _i, _p]),
 }
 
 _lib = None

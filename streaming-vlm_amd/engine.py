@@ -29,6 +29,8 @@ from .positions import rope_index_1d, rope_index_qwen2, rope_index_qwen2_5
 from .weights import EngineWeights
 
 BF16 = torch.bfloat16
+# ops entry points an llm_fp8 engine needs (csrc/decode_fp8.hip)
+FP8_LLM_OPS = ("dec_qkv_fp8", "dec_gate_up_fp8", "gemv_fp8", "dec_lm_head_fp8", "dequant_fp8")
 
 
 @dataclass
@@ -245,7 +247,7 @@ class SvlmEngine:
     def __init__(self, cfg: ModelConfig, state_dict, device="cuda", ops=None, max_len: int = 4096, max_new_tokens: int = 32,
                  decode_chunk: Optional[int] = None, use_graph: Optional[bool] = None, kv_slack: float = 1.0, kv_page_tokens: int = 16,
                  decode_tail: Optional[bool] = None,
-                 vit_fp8: bool = False, linear_planes: Optional[bool] = None):
+                 vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False):
         if ops is None:
             from .ops import HipOps
             ops = HipOps()                      # raises when the HIP extension / GPU is missing
@@ -255,7 +257,18 @@ class SvlmEngine:
         # the cache keeps the rotated keys / values the prefill gathers (kv_pool.py: linear planes) and the decode steps stream them;
         # False: no second copy of the K/V rows, every decode step rotates the pool rows (same bits)
         self.linear_planes = (os.environ.get("SVLM_LINEAR_PLANES", "1") != "0") if linear_planes is None else bool(linear_planes)
-        self.w = EngineWeights(state_dict, cfg, self.device)
+        # opt-in fp8 language model: e4m3 layer matrices and lm_head with power-of-two row scales (weights.py:quantize_rows_fp8_pow2);
+        # the decode step streams them through the fp8 GEMVs, the prefill dequantises each layer into one bf16 scratch layer and runs
+        # the bf16 GEMMs on it.  It computes exactly the bf16 model on W' = weights.fp8_reference_state_dict(state_dict).
+        self.llm_fp8 = bool(llm_fp8)
+        if self.llm_fp8:
+            missing = [m for m in FP8_LLM_OPS if not hasattr(ops, m)]
+            if missing:
+                raise ValueError(f"llm_fp8=True needs an ops backend with the fp8 entry points; {type(ops).__name__} lacks {missing}")
+            if decode_tail or (decode_tail is None and os.environ.get("SVLM_DECODE_TAIL", "0") == "1"):
+                raise ValueError("llm_fp8=True cannot be combined with decode_tail=True (the persistent layer tail streams bf16 weights)")
+        self.w = EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8)
+        self._fp8_scratch = None           # llm_fp8: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
         tc, vc = cfg.text, cfg.vision
         if tc.head_dim != 128 or sum(tc.mrope_section) * 2 != tc.head_dim:
             raise ValueError("LLM head_dim must be 128 with mrope sections summing to 64")
@@ -548,6 +561,8 @@ class SvlmEngine:
         lin = c.lin_args() if hasattr(c, "lin_args") else None
         o.rmsnorm(x, w.layers[0]["ln1"], tc.rms_eps, out=xn)
         for li, lw in enumerate(w.layers):
+            if self.llm_fp8:
+                lw = self._dequant_layer(lw)
             o.gemm(xn, lw["qkv_w"], bias=lw["qkv_b"], out=qkv)
             # the chunk's K/V rows go to their pool slots inside the launch that rotates and gathers the keys
             o.prefill_attn(qkv[:, :qd], c.pool, li, c.slot_of_dev, self.rope_cs, attn, T, L, tc.num_heads, scale,
@@ -572,7 +587,25 @@ class SvlmEngine:
             return
         last = x[T - 1:T].contiguous()
         o.rmsnorm(last, w.final_norm, tc.rms_eps, out=self.d_xn.view(1, H))
-        o.gemv(self.d_xn, w.lm_head, out_f32=self.logits)
+        if self.llm_fp8:
+            o.gemv_fp8(self.d_xn, w.lm_head8, w.lm_head_s, out_f32=self.logits)
+        else:
+            o.gemv(self.d_xn, w.lm_head, out_f32=self.logits)
+
+    def _dequant_layer(self, lw):
+        """llm_fp8 prefill: the layer's four matrices as bf16 W' in the (reused) scratch layer; the layer dict with those views."""
+        sc = self._fp8_scratch
+        if sc is None:
+            flat = torch.empty(lw["flat8"].numel(), dtype=BF16, device=self.device)
+            sc, off = {}, 0
+            for name in ("qkv_w", "o_w", "gu_w", "down_w"):
+                n = lw[name + "8"].numel()
+                sc[name] = flat[off:off + n].view(lw[name + "8"].shape)
+                off += n
+            self._fp8_scratch = sc
+        for name, dst in sc.items():
+            self.ops.dequant_fp8(lw[name + "8"], lw[name + "_s"], dst)
+        return dict(lw, **sc)
 
     def _decode_step_launch(self, c: KVPool):
         """One token, 6 launches per layer: [norm+QKV+append] [attn split] [attn combine] [o+res] [norm+gate/up+SwiGLU]
@@ -597,7 +630,7 @@ class SvlmEngine:
                     ln = w.layers[li + 1]
                     nxt = (ln["ln1"], ln["qkv_w"], ln["qkv_b"], self.d_qkv, c.pool, li + 1, c.slot_of_dev, qd, kd, 0, kv_len)
                 o.dec_tail(self.d_attn, self.d_x, lw["o_w"], lw["ln2"], lw["gu_w"], lw["down_w"], tc.rms_eps, self.tail_ws, li, nl, nxt=nxt)
-        for li, lw in enumerate(w.layers if not self.decode_tail else ()):
+        for li, lw in enumerate(w.layers if not (self.decode_tail or self.llm_fp8) else ()):
             o.dec_qkv(self.d_x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.d_qkv, c.pool, li, c.slot_of_dev, qd, kd,
                       len_dev=kv_len, lin=lin)
             o.decode_attn(self.d_qkv[:qd], c.pool, li, c.slot_of_dev, self.rope_cs, self.d_attn, self.d_ws, tc.num_heads,
@@ -605,13 +638,27 @@ class SvlmEngine:
             o.gemv(self.d_attn, lw["o_w"], residual=self.d_x, out=self.d_x)
             o.dec_gate_up(self.d_x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.d_h)
             o.gemv(self.d_h, lw["down_w"], residual=self.d_x, out=self.d_x)
+        for li, lw in enumerate(w.layers if self.llm_fp8 else ()):
+            # the same launches with the four weight-streaming GEMVs on e4m3 weights (csrc/decode_fp8.hip)
+            o.dec_qkv_fp8(self.d_x, lw["ln1"], tc.rms_eps, lw["qkv_w8"], lw["qkv_w_s"], lw["qkv_b"], self.d_qkv, c.pool, li, c.slot_of_dev, qd, kd,
+                          len_dev=kv_len, lin=lin)
+            o.decode_attn(self.d_qkv[:qd], c.pool, li, c.slot_of_dev, self.rope_cs, self.d_attn, self.d_ws, tc.num_heads,
+                          self._attn_len, self.decode_chunk, scale, length=1, len_dev=kv_len, lin=lin)
+            o.gemv_fp8(self.d_attn, lw["o_w8"], lw["o_w_s"], residual=self.d_x, out=self.d_x)
+            o.dec_gate_up_fp8(self.d_x, lw["ln2"], tc.rms_eps, lw["gu_w8"], lw["gu_w_s"], self.d_h)
+            o.gemv_fp8(self.d_h, lw["down_w8"], lw["down_w_s"], residual=self.d_x, out=self.d_x)
         smp = self._sampling
-        if smp is not None and smp[1] == 0 and smp[2] >= 1.0:     # plain temperature sampling: Gumbel-max inside the candidates
-            o.dec_lm_head(self.d_x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.seen if self._penalty != 1.0 else None,
-                          self._penalty, self._suppress, self.d_sws, temperature=smp[0], rng=self.rng_dev, state=self.state)
+        seen = self.seen if self._penalty != 1.0 else None
+        if self.llm_fp8:
+            head = lambda **kw: o.dec_lm_head_fp8(self.d_x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, seen, self._penalty,
+                                                  self._suppress, self.d_sws, **kw)
         else:
-            o.dec_lm_head(self.d_x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.seen if self._penalty != 1.0 else None,
-                          self._penalty, self._suppress, self.d_sws)
+            head = lambda **kw: o.dec_lm_head(self.d_x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, seen, self._penalty, self._suppress,
+                                              self.d_sws, **kw)
+        if smp is not None and smp[1] == 0 and smp[2] >= 1.0:     # plain temperature sampling: Gumbel-max inside the candidates
+            head(temperature=smp[0], rng=self.rng_dev, state=self.state)
+        else:
+            head()
 
     def _sample_launch(self, advance_kv: int, fused: bool = False):
         """Token choice + device-side feedback (tok_buf / state / seen).  `fused`: dec_lm_head already left its candidates in

@@ -630,3 +630,85 @@ class HipOps:
         _req(ws, torch.float32, "argmax_finish.ws", 1); _req(tok_buf, torch.int32, "argmax_finish.tok_buf", 1)
         _req(state, torch.int32, "argmax_finish.state", 1)
         check(self.lib.svlm_argmax_finish(_ptr(ws), V, _ptr(seen), _ptr(tok_buf), _ptr(state), int(advance_kv), _stream()), "svlm_argmax_finish")
+
+    # ------------------------------------------------------------------ fp8 language-model weights (csrc/decode_fp8.hip)
+    @staticmethod
+    def _req_fp8(W8, scale, name):
+        _req(W8, torch.float8_e4m3fn, f"{name}.W8", 2); _req(scale, torch.float32, f"{name}.w_scale", 1)
+        N, K = W8.shape
+        if scale.numel() != N or K % 16 or W8.stride(0) % 16:
+            raise _lib.SvlmError(f"{name}: W8 {tuple(W8.shape)} (stride {W8.stride(0)}) needs K and row stride multiples of 16 and "
+                                 f"one scale per row (got {scale.numel()})")
+        return N, K
+
+    def dec_qkv_fp8(self, x, ln_w, eps, W8, w_scale, bias, q_out, pool, layer, slot_of, qd, kd, length=0, len_dev=None, lin=None):
+        """dec_qkv on e4m3 rows with per-row scales."""
+        _req(x, BF16, "dec_qkv_fp8.x", 1); _req(ln_w, BF16, "dec_qkv_fp8.ln_w", 1)
+        _req(bias, BF16, "dec_qkv_fp8.bias", 1); _req(q_out, BF16, "dec_qkv_fp8.q_out", 1); _req(slot_of, torch.int32, "dec_qkv_fp8.slot_of", 1)
+        N, K = self._req_fp8(W8, w_scale, "dec_qkv_fp8")
+        _, _, Hkv, n_slots, D = pool.shape
+        assert N == qd + 2 * kd == bias.numel() and kd == Hkv * D and x.numel() == K == ln_w.numel() and q_out.numel() >= qd
+        if len_dev is None:
+            assert 0 <= length < slot_of.numel()
+        kp, vp = self._planes(pool, layer)
+        kl, vl, lin_rows, _ = self._lin_args(lin, layer, Hkv, D, length + 1 if len_dev is None else 1, "dec_qkv_fp8")
+        check(self.lib.svlm_dec_qkv_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(q_out), _ptr(kp),
+                                        _ptr(vp), _ptr(slot_of), _ptr(len_dev), int(length), K, qd, kd, D, n_slots, _ptr(kl), _ptr(vl), lin_rows,
+                                        _stream()), "svlm_dec_qkv_fp8")
+
+    def dec_gate_up_fp8(self, x, ln_w, eps, W8, w_scale, h):
+        _req(x, BF16, "dec_gate_up_fp8.x", 1); _req(ln_w, BF16, "dec_gate_up_fp8.ln_w", 1); _req(h, BF16, "dec_gate_up_fp8.h", 1)
+        N, K = self._req_fp8(W8, w_scale, "dec_gate_up_fp8")
+        assert N % 2 == 0 and h.numel() == N // 2 and x.numel() == K == ln_w.numel()
+        check(self.lib.svlm_dec_gate_up_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(h), N // 2, K, _stream()),
+              "svlm_dec_gate_up_fp8")
+
+    def gemv_fp8(self, x, W8, w_scale, bias=None, residual=None, out=None, out_f32=None):
+        _req(x, BF16, "gemv_fp8.x")
+        N, K = self._req_fp8(W8, w_scale, "gemv_fp8")
+        if x.numel() != K:
+            raise _lib.SvlmError(f"gemv_fp8: x has {x.numel()} elements, W8 is {tuple(W8.shape)}")
+        if out is None and out_f32 is None:
+            out = torch.empty((N,), dtype=BF16, device=x.device)
+        if out is not None:
+            _req(out, BF16, "gemv_fp8.out"); assert out.numel() == N
+        if out_f32 is not None:
+            _req(out_f32, torch.float32, "gemv_fp8.out_f32"); assert out_f32.numel() == N
+        if bias is not None:
+            _req(bias, BF16, "gemv_fp8.bias"); assert bias.numel() == N
+        if residual is not None:
+            _req(residual, BF16, "gemv_fp8.residual"); assert residual.numel() == N
+        check(self.lib.svlm_gemv_fp8(_ptr(x), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_f32),
+                                     N, K, ACT_NONE, _stream()), "svlm_gemv_fp8")
+        return out if out is not None else out_f32
+
+    def dec_lm_head_fp8(self, x, ln_w, eps, W8, w_scale, logits, seen, penalty, suppress, ws, temperature=None, rng=None, state=None):
+        """dec_lm_head on e4m3 rows: the same candidates in `ws`, completed by argmax_finish."""
+        _req(x, BF16, "dec_lm_head_fp8.x", 1); _req(ln_w, BF16, "dec_lm_head_fp8.ln_w", 1)
+        _req(logits, torch.float32, "dec_lm_head_fp8.logits", 1); _req(ws, torch.float32, "dec_lm_head_fp8.ws", 1)
+        V, K = self._req_fp8(W8, w_scale, "dec_lm_head_fp8")
+        assert logits.numel() == V and x.numel() == K == ln_w.numel()
+        assert ws.numel() * 4 >= self.lib.svlm_dec_lm_head_ws_bytes(V)
+        n_sup = 0
+        if seen is not None:
+            _req(seen, torch.uint8, "dec_lm_head_fp8.seen", 1); assert seen.numel() == V
+        if suppress is not None:
+            _req(suppress, torch.int32, "dec_lm_head_fp8.suppress", 1)
+            n_sup = suppress.numel()
+        if rng is not None:
+            _req(rng, torch.int32, "dec_lm_head_fp8.rng", 1); _req(state, torch.int32, "dec_lm_head_fp8.state", 1)
+            check(self.lib.svlm_dec_lm_head_sample_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(logits),
+                                                       _ptr(seen), float(penalty), _ptr(suppress), n_sup, _ptr(ws), V, K, float(temperature),
+                                                       _ptr(rng), _ptr(state), _stream()), "svlm_dec_lm_head_sample_fp8")
+            return
+        check(self.lib.svlm_dec_lm_head_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(logits), _ptr(seen),
+                                            float(penalty), _ptr(suppress), n_sup, _ptr(ws), V, K, _stream()), "svlm_dec_lm_head_fp8")
+
+    def dequant_fp8(self, W8, w_scale, out):
+        """out = bf16(W8 * w_scale[:, None]) (exact for power-of-two scales); contiguous matrices of equal shape."""
+        N, K = self._req_fp8(W8, w_scale, "dequant_fp8")
+        _req(out, BF16, "dequant_fp8.out", 2)
+        if tuple(out.shape) != (N, K) or not W8.is_contiguous() or not out.is_contiguous():
+            raise _lib.SvlmError(f"dequant_fp8: out {tuple(out.shape)} vs W8 {tuple(W8.shape)}, both contiguous")
+        check(self.lib.svlm_dequant_fp8_bf16(_ptr(W8), _ptr(w_scale), _ptr(out), N, K, _stream()), "svlm_dequant_fp8_bf16")
+        return out

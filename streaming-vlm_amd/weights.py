@@ -130,10 +130,55 @@ def decisive_state_dict(cfg: ModelConfig, seed: int = 0, device="cpu", dtype=tor
     return sd
 
 
-class EngineWeights:
-    """Fused, contiguous, device-resident views the kernels consume."""
+LLM_FP8_MATRICES = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+                    "mlp.down_proj")
 
-    def __init__(self, sd: Dict[str, torch.Tensor], cfg: ModelConfig, device):
+
+def quantize_rows_fp8_pow2(w: torch.Tensor):
+    """Per output row n: s_n = 2^ceil(log2(amax_n / 448)) (exactly: frexp of amax_n / 448 in fp64, whose 53 bits cannot round a
+    value above a power of two onto it), zero rows s_n = 1; q = rne_e4m3(w / s_n), which never saturates since |w / s_n| <= 448.
+    Returns (q float8_e4m3fn [N, K], s float32 [N]).  W' = q * s_n is exactly representable in bf16, so a GEMV that applies s_n
+    once to sum_k q_k x_k computes the bf16 GEMV on W' up to the fp32 summation order."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    m, e = torch.frexp(amax.double() / 448.0)                # amax / 448 = m * 2^e, m in [0.5, 1)
+    e = torch.where(m == 0.5, e - 1, e)                      # already a power of two: that value
+    e = e.clamp(min=-126)                                    # (a scale never needs to be subnormal: the row only gets smaller)
+    s = torch.where(amax > 0, torch.pow(2.0, e.double()).float(), torch.ones_like(amax))      # (2^e exact in fp64 and fp32)
+    q = (wf / s.unsqueeze(1)).to(torch.float8_e4m3fn)
+    return q, s.contiguous()
+
+
+def dequantize_rows_fp8(q: torch.Tensor, s: torch.Tensor, dtype=torch.bfloat16):
+    """W' = q * s_n (exact in bf16)."""
+    return (q.float() * s.float().unsqueeze(1)).to(dtype)
+
+
+def fp8_reference_state_dict(sd: Dict[str, torch.Tensor], cfg: ModelConfig) -> Dict[str, torch.Tensor]:
+    """The model an `llm_fp8=True` engine built from `sd` computes, as a bf16 state dict: every LLM layer matrix (q/k/v/o_proj,
+    gate/up/down_proj) and the lm_head replaced by W' = dequant(quant(W)).  Biases, norms, the embedding table and the whole vision
+    tower stay as they are; with tied embeddings an explicit `lm_head.weight` = W'(embed) is added (the embedding gather keeps
+    reading the bf16 table)."""
+    tc = cfg.text
+    out = dict(sd)
+    for i in range(tc.num_layers):
+        for m in LLM_FP8_MATRICES:
+            k = f"{L_PREFIX}layers.{i}.{m}.weight"
+            out[k] = dequantize_rows_fp8(*quantize_rows_fp8_pow2(sd[k]), dtype=sd[k].dtype)
+    head = sd[L_PREFIX + "embed_tokens.weight"] if tc.tie_word_embeddings else sd["lm_head.weight"]
+    out["lm_head.weight"] = dequantize_rows_fp8(*quantize_rows_fp8_pow2(head), dtype=head.dtype)
+    return out
+
+
+class EngineWeights:
+    """Fused, contiguous, device-resident views the kernels consume.
+
+    `llm_fp8`: the LLM layer matrices and the lm_head are kept as e4m3 with one power-of-two scale per row (quantize_rows_fp8_pow2),
+    quantised layer by layer so that no bf16 copy of all layers ever exists; per layer `flat8` (qkv | o | gate/up | down, back to
+    back) and `scale` (their rows' scales, same order) with the views `<name>8` / `<name>_s`; `lm_head8` / `lm_head_s`.  The bf16
+    embedding table stays."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], cfg: ModelConfig, device, llm_fp8: bool = False):
         vc, tc = cfg.vision, cfg.text
         want = state_dict_shapes(cfg)
         missing = [k for k in want if k not in sd]
@@ -179,7 +224,16 @@ class EngineWeights:
             self.merger = {k: dev(sd[m + n]) for k, n in [("ln_w", "ln_q.weight"), ("ln_b", "ln_q.bias"), ("w0", "mlp.0.weight"),
                                                            ("b0", "mlp.0.bias"), ("w2", "mlp.2.weight"), ("b2", "mlp.2.bias")]}
         self.embed = dev(sd[L_PREFIX + "embed_tokens.weight"])
-        self.lm_head = self.embed if tc.tie_word_embeddings else dev(sd["lm_head.weight"])
+        self.llm_fp8 = bool(llm_fp8)
+        if self.llm_fp8:
+            for name, K in (("hidden", tc.hidden_size), ("q width", tc.num_heads * tc.head_dim), ("intermediate", tc.intermediate_size)):
+                if K % 16:
+                    raise ValueError(f"llm_fp8 needs K a multiple of 16 (one 16-B load = 16 weights): {name} is {K}")
+            self.lm_head = None
+            self.lm_head8, self.lm_head_s = quantize_rows_fp8_pow2(
+                (self.embed if tc.tie_word_embeddings else sd["lm_head.weight"]).to(device=device))
+        else:
+            self.lm_head = self.embed if tc.tie_word_embeddings else dev(sd["lm_head.weight"])
         self.final_norm = dev(sd[L_PREFIX + "norm.weight"])
         self.layers = []
         for i in range(tc.num_layers):
@@ -190,6 +244,9 @@ class EngineWeights:
             # the four matrices of a layer live back to back in ONE buffer (streamed in this order by a decode step),
             # so the next layer can be pulled into the Infinity Cache with a single range prefetch
             mats = [("qkv_w", qkv_w), ("o_w", sd[p + "self_attn.o_proj.weight"]), ("gu_w", gu_w), ("down_w", sd[p + "mlp.down_proj.weight"])]
+            if self.llm_fp8:
+                self.layers.append(self._fp8_layer(sd, p, qkv_b, mats, device, dev))
+                continue
             flat = torch.empty(sum(m.numel() for _, m in mats), dtype=torch.bfloat16, device=device)
             layer = dict(ln1=dev(sd[p + "input_layernorm.weight"]), ln2=dev(sd[p + "post_attention_layernorm.weight"]), qkv_b=dev(qkv_b), flat=flat)
             off = 0
@@ -200,9 +257,37 @@ class EngineWeights:
                 off += m.numel()
             self.layers.append(layer)
 
-    def nbytes_llm_decode(self) -> int:
-        """Weight bytes one decode step streams (layers + final norm + lm_head)."""
-        n = self.lm_head.numel() + self.final_norm.numel()
+    @staticmethod
+    def _fp8_layer(sd, p, qkv_b, mats, device, dev):
+        """One layer in e4m3: each matrix is quantised on `device` on its own, so at most one bf16 matrix exists beside the fp8 ones."""
+        rows = sum(m.shape[0] for _, m in mats)
+        flat8 = torch.empty(sum(m.numel() for _, m in mats), dtype=torch.float8_e4m3fn, device=device)
+        scale = torch.empty(rows, dtype=torch.float32, device=device)
+        layer = dict(ln1=dev(sd[p + "input_layernorm.weight"]), ln2=dev(sd[p + "post_attention_layernorm.weight"]), qkv_b=dev(qkv_b),
+                     flat8=flat8, scale=scale)
+        off = r0 = 0
+        for name, m in mats:
+            q, s8 = quantize_rows_fp8_pow2(m.to(device=device))
+            view = flat8[off:off + m.numel()].view(m.shape)
+            view.copy_(q)
+            scale[r0:r0 + m.shape[0]].copy_(s8)
+            layer[name + "8"] = view
+            layer[name + "_s"] = scale[r0:r0 + m.shape[0]]
+            del q, s8
+            off += m.numel()
+            r0 += m.shape[0]
+        return layer
+
+    def decode_bytes(self) -> int:
+        """Weight bytes one decode step streams (layers + final norm + lm_head): e4m3 codes and their row scales with `llm_fp8`."""
+        n = self.final_norm.numel() * 2
+        if self.llm_fp8:
+            n += self.lm_head8.numel() + self.lm_head_s.numel() * 4
+        else:
+            n += self.lm_head.numel() * 2
         for l in self.layers:
-            n += sum(t.numel() for k, t in l.items() if k != "flat")
-        return n * 2
+            n += sum(t.numel() * t.element_size() for k, t in l.items() if k not in ("flat", "flat8", "scale"))
+        return n
+
+    def nbytes_llm_decode(self) -> int:
+        return self.decode_bytes()
