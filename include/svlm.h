@@ -319,6 +319,50 @@ int svlm_dec_lm_head_sample_fp8(const void* x, const void* ln_w, float eps, cons
  * which the prefill GEMMs read.  replaces: nothing (the reference has bf16 weights; this rebuilds them from the fp8 copy). */
 int svlm_dequant_fp8_bf16(const void* src8, const float* scale, void* dst, int rows, int cols, void* stream);
 
+/* ---- stream groups: lane-batched decode step (csrc/decode_batch.hip; stream_group.py).  B = 1..4 independent streams ("lanes") on
+ * one GPU and ONE weight set take their decode step together: every kernel below reads each weight row once and multiplies it with the
+ * B activation rows of the group.  Per (lane, output row) the FMA order, the reductions and every bf16 rounding point are those of the
+ * single-row entry, so each lane's outputs are BITWISE what that entry computes for the lane alone.
+ * Activations are group-owned [B, .] row-major buffers with a row stride (ld*, in elements); everything a lane owns comes from the lane
+ * table: B consecutive svlm_lane records in device memory, written by the host when a lane starts a chunk.  A lane is LIVE in a step
+ * iff state[1] + 1 < limit; a lane that is not live is skipped by every entry: no KV row, no token, state / seen / tok_buf untouched
+ * (its rows of the group buffers are left as they are). */
+typedef struct svlm_lane {
+  void* pool;           /* the lane's KV pool [n_layers][2][Hkv][n_slots][D] bf16 */
+  void* lin;            /* its linear planes [n_layers][2][Hkv][lin_rows][D] bf16 (see svlm_decode_attn_lin), or NULL */
+  const int* slot_of;   /* logical row -> slot */
+  int* state;           /* {kv_len, cur} as svlm_penalty_argmax */
+  int* tok_buf;
+  unsigned char* seen;  /* [V] repetition-penalty marks, or NULL */
+  int limit;            /* tokens this chunk may produce (max_new_tokens); 0 parks the lane */
+  int n_slots;
+  int lin_rows;
+  float penalty;        /* repetition penalty (> 0; used with seen) */
+  int n_suppress;       /* how many entries of the launch's `suppress` list apply to this lane (0 = EOS allowed) */
+  int pad_;
+} svlm_lane;            /* 72 bytes */
+/* x[b] = table[tok_buf_b[state_b[1]]] (cols bf16 per row).  replaces: the embed_tokens call of a decode step (qwen2/model_forward.py:33). */
+int svlm_decb_embed(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream);
+/* svlm_dec_qkv_lin for B lanes: q rows to q_out[b], the new K/V rows to each lane's own pool slot slot_of[state[0]] of `layer` and to
+ * its linear planes.  head_dim 128.  replaces: qwen2/language_forward.py:183,80-82 + generate/streaming_cache.py:72-73. */
+int svlm_decb_qkv(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw, const void* bias,
+                  void* q_out, int ldq, int layer, int K, int qd, int kd, int D, void* stream);
+/* svlm_dec_gate_up for B lanes.  replaces: qwen2/language_forward.py:200-201 (Qwen2MLP). */
+int svlm_decb_gate_up(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw, void* h,
+                      int ldh, int I, int K, void* stream);
+/* svlm_gemv_bf16 with residual for B lanes: y[b] = bf16(bf16(W x[b]) + residual[b]); y may be residual.  The shapes the single-row
+ * entry splits over K are split the same way.  replaces: o_proj / down_proj at T = 1 (qwen2/language_forward.py:161,201). */
+int svlm_decb_gemv(const void* lanes, int B, const void* x, int ldx, const void* W, int ldw, const void* residual, int ldr, void* y,
+                   int ldy, int N, int K, void* stream);
+/* svlm_dec_lm_head (greedy) for B lanes: fp32 logits rows, per-lane penalty / suppression from the lane table, candidates of lane b at
+ * ws + b * svlm_decb_lm_head_ws_stride(V) in the layout of svlm_dec_lm_head; svlm_decb_argmax_finish (one workgroup per lane) picks
+ * each live lane's winner and feeds it back as svlm_argmax_finish does.
+ * replaces: qwen2/language_forward.py:315, qwen2/model_forward.py:243, generate/streaming_generate_qwen.py:73-104. */
+long long svlm_decb_lm_head_ws_stride(int V); /* [host] */
+int svlm_decb_lm_head(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw, float* logits,
+                      int ldl, const int* suppress, void* ws, int V, int K, void* stream);
+int svlm_decb_argmax_finish(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

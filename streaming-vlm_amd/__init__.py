@@ -20,5 +20,7 @@ from .driver import (contiguous_id_and_kv, load_model_and_processor, open_vtt, p
 from .synthetic import (DeviceFrameProcessor, PinnedVideo, SyntheticProcessor, SyntheticVideo, patchify,  # noqa: F401
                         synthetic_frame)
 from .weights import random_state_dict  # noqa: F401
+from .stream_group import StreamGroup  # noqa: F401
+from .multi_stream import StreamGroupError, streaming_inference_group  # noqa: F401
 
 __version__ = "0.1.0"

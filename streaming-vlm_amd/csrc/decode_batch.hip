@@ -1,0 +1,533 @@
+// Lane-batched decode-step kernels: B independent streams ("lanes", B = 1..4) take their decode step together, so that every
+// weight byte is read ONCE and every launch boundary is paid ONCE for B tokens.
+//
+//   svlm_decb_embed          x[b] = embed[tok_buf_b[cur_b]]                                       (the step's embedding gather)
+//   svlm_decb_qkv            batched svlm_dec_qkv_lin: RMSNorm + QKV + bias + KV append to each lane's own pool slot / linear planes
+//   svlm_decb_gemv           batched svlm_gemv_bf16 with residual (o_proj, down_proj), K split over the workgroup's waves for the
+//                            same shapes as the single-row entry
+//   svlm_decb_gate_up        batched svlm_dec_gate_up
+//   svlm_decb_lm_head        batched svlm_dec_lm_head (greedy: penalty, suppression, argmax candidates per lane)
+//   svlm_decb_argmax_finish  batched svlm_argmax_finish, one workgroup per lane
+//
+// Each wave loads its weight rows once (the same 16-B non-temporal loads and PRE run-ahead as decode_fused.hip) and multiplies them
+// with the NB activation rows of the group.  The fused kernels stage the NB normalised rows in LDS; svlm_decb_gemv reads its NB
+// un-normalised rows straight from global memory like svlm_gemv_bf16 does (a down_proj row of 4 lanes is 150 KB: it does not fit a
+// workgroup's LDS share, and the rows are L2-resident).
+//
+// ARITHMETIC ORDER IS KEPT PER LANE: for one (lane, output row) the FMA sequence over K, the wave_sum, the K-split reduction
+// part[0] + part[1] + part[2] + part[3] and every bf16 rounding point are those of the single-row kernel (whose device functions are
+// shared through dec_xrow.h / dec_stream.h), so every output is bitwise the single-row kernel's.  How many rows a wave takes does not
+// enter a row's arithmetic; only svlm_decb_lm_head must keep the single-row kernel's 8 vocabulary rows per workgroup, because the
+// candidates are per workgroup.
+//
+// Per-lane pointers come from the LANE TABLE (struct svlm_lane, include/svlm.h).  A lane is LIVE in a step iff
+// state[1] + 1 < limit; a lane that is not live is skipped by every kernel: no KV row, no token, no state change.
+#include "common.h"
+#include "dec_xrow.h"
+#include "dec_stream.h"
+
+struct svlm_lane {                 // mirror of include/svlm.h
+  bf16_t* pool;                    // [n_layers][2][Hkv][n_slots][D]
+  bf16_t* lin;                     // [n_layers][2][Hkv][lin_rows][D] or null
+  const int* slot_of;
+  int* state;                      // {kv_len, cur}
+  int* tok_buf;
+  unsigned char* seen;             // [V] or null (no repetition penalty)
+  int limit;                       // live while state[1] + 1 < limit
+  int n_slots;
+  int lin_rows;
+  float penalty;
+  int n_suppress;
+  int pad_;
+};
+static_assert(sizeof(svlm_lane) == 72, "svlm_lane layout (include/svlm.h)");
+
+__device__ __forceinline__ bool lane_live(const svlm_lane& L) { return L.state[1] + 1 < L.limit; }
+
+// acc[b][r] += W[row r] . xs[b] over the PRE K-steps held in `pre`; per (b, r) the same FMA sequence as fma_batch (decode_fused.hip)
+template <int NB, int NR, int PRE>
+__device__ __forceinline__ void fma_batch_b(const WPre<NR, PRE>& pre, const bf16_t* xs, int base, int K, float (&acc)[NB][NR]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int it = 0; it < PRE; ++it) {
+    const int c = base + it * 512 + lane * 8;
+    float wf[NR][8];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) unpack8(pre.w[it][r], wf[r]);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      float xf[8];
+      unpack8(*reinterpret_cast<const u32x4_t*>(xs + (size_t)b * K + (c < K ? c : 0)), xf);
+      if (c >= K) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) xf[i] = 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[b][r] = fmaf(wf[r][i], xf[i], acc[b][r]);
+      }
+    }
+  }
+}
+
+template <int NB, int NR, int PRE>
+__device__ __forceinline__ void wave_dots_b(const bf16_t* const (&wr)[NR], const bf16_t* xs, int K, float (&acc)[NB][NR], WPre<NR, PRE>& pre) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[b][r] = 0.f;
+  fma_batch_b<NB, NR, PRE>(pre, xs, 0, K, acc);
+  for (int base = PRE * 512; base < K; base += PRE * 512) {
+    preload_w<NR, PRE>(wr, base, K, pre);
+    __builtin_amdgcn_sched_barrier(0);
+    fma_batch_b<NB, NR, PRE>(pre, xs, base, K, acc);
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[b][r] = wave_sum(acc[b][r]);
+}
+
+// Prologue of the fused kernels: the live lanes' x rows are requested first, then the head of the weight stream, then the rows are
+// normalised and staged one after the other (xs[b * K ..]); a lane that is not live leaves its LDS row as it is (its products are
+// never written).
+template <int NB, int XC>
+__device__ __forceinline__ void load_rows(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                          const bf16_t* __restrict__ ln_w, int K, XRow<XC> (&xr)[NB], bool (&live)[NB]) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    live[b] = lane_live(lanes[b]);
+    if (live[b]) load_x<XC>(x + (size_t)b * ldx, ln_w, K, xr[b]);
+  }
+}
+template <int NB, int XC>
+__device__ __forceinline__ void stage_rows(const XRow<XC> (&xr)[NB], const bool (&live)[NB], float eps, int K, bf16_t* xs) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+    if (live[b]) stage_x<XC>(xr[b], eps, K, xs + (size_t)b * K);          // (workgroup-uniform branch: barriers inside)
+}
+
+// ---------------------------------------------------------------- embedding gather
+__global__ __launch_bounds__(256) void decb_embed_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ table,
+                                                         bf16_t* __restrict__ x, int ldx, int cols, int n_rows) {
+  const svlm_lane& L = lanes[blockIdx.y];
+  if (!lane_live(L)) return;
+  int id = L.tok_buf[L.state[1]];
+  id = min(max(id, 0), n_rows - 1);
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 8;
+  if (c < cols)
+    *reinterpret_cast<u32x4_t*>(x + (size_t)blockIdx.y * ldx + c) = *reinterpret_cast<const u32x4_t*>(table + (size_t)id * cols + c);
+}
+
+// ---------------------------------------------------------------- QKV + KV append
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_qkv_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                       const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
+                                                       const bf16_t* __restrict__ bias, bf16_t* __restrict__ q_out, int ldq, int layer,
+                                                       int N, int K, int qd, int kd, int D) {
+  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + wave;
+  const bf16_t* wr[1] = {W + (size_t)min(n, N - 1) * ldw};
+  XRow<XC> xr[NB];
+  bool live[NB];
+  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
+  __builtin_amdgcn_sched_barrier(0);
+  WPre<1, PRE> pre;
+  preload_w<1, PRE>(wr, 0, K, pre);
+  const bf16_t bpre = bias[min(n, N - 1)];
+  __builtin_amdgcn_sched_barrier(0);
+  stage_rows<NB, XC>(xr, live, eps, K, xs);
+  if (n >= N) return;
+  float acc[NB][1];
+  wave_dots_b<NB, 1, PRE>(wr, xs, K, acc, pre);
+  if (lane == 0) {
+    const int Hkv = kd / D;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (!live[b]) continue;
+      const svlm_lane& L = lanes[b];
+      const bf16_t v = f2bf(acc[b][0] + bf2f(bpre));
+      if (n < qd) {
+        q_out[(size_t)b * ldq + n] = v;
+      } else {
+        const int row = L.state[0];
+        const int slot = L.slot_of[row];
+        const int j = n - qd;
+        const int jj = j < kd ? j : j - kd;
+        const int h = jj / D, d = jj % D;
+        bf16_t* plane = L.pool + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.n_slots * D;
+        plane[((size_t)h * L.n_slots + slot) * D + d] = v;
+        if (L.lin != nullptr) {      // as svlm_dec_qkv_lin: the key UN-rotated in its tile position, the value as it is, at logical row `row`
+          bf16_t* lp = L.lin + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.lin_rows * D;
+          if (j < kd) lp[((size_t)h * (L.lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
+          else lp[((size_t)h * L.lin_rows + row) * D + d] = v;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- gate/up + SwiGLU
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_gate_up_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                           const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
+                                                           bf16_t* __restrict__ h, int ldh, int I, int K) {
+  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + wave;
+  const int nc = min(n, I - 1);
+  const bf16_t* wr[2] = {W + (size_t)nc * ldw, W + (size_t)(I + nc) * ldw};       // gate row n, up row n
+  XRow<XC> xr[NB];
+  bool live[NB];
+  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
+  __builtin_amdgcn_sched_barrier(0);
+  WPre<2, PRE> pre;
+  preload_w<2, PRE>(wr, 0, K, pre);
+  __builtin_amdgcn_sched_barrier(0);
+  stage_rows<NB, XC>(xr, live, eps, K, xs);
+  if (n >= I) return;
+  float acc[NB][2];
+  wave_dots_b<NB, 2, PRE>(wr, xs, K, acc, pre);
+  if (lane == 0) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (!live[b]) continue;
+      const float g = rbf(acc[b][0]), u = rbf(acc[b][1]);
+      h[(size_t)b * ldh + n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- lm_head + penalty + argmax candidates
+#define DECB_LM_ROWS 2            // = LM_ROWS of decode_fused.hip: the candidates are per workgroup of 4 x LM_ROWS vocabulary rows
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                           const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
+                                                           float* __restrict__ logits, int ldl, const int* __restrict__ suppress,
+                                                           float* __restrict__ ws, long long ws_stride, int V, int K) {
+  constexpr int ROWS = DECB_LM_ROWS;
+  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
+  const bf16_t* wr[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, V - 1) * ldw;
+  XRow<XC> xr[NB];
+  bool live[NB];
+  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
+  __builtin_amdgcn_sched_barrier(0);
+  WPre<ROWS, PRE> pre;
+  preload_w<ROWS, PRE>(wr, 0, K, pre);
+  __builtin_amdgcn_sched_barrier(0);
+  stage_rows<NB, XC>(xr, live, eps, K, xs);
+  float best[NB];
+  int bi[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) { best[b] = -INFINITY; bi[b] = 0x7fffffff; }
+  if (n0 < V) {
+    float acc[NB][ROWS];
+    wave_dots_b<NB, ROWS, PRE>(wr, xs, K, acc, pre);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (!live[b]) continue;
+      const svlm_lane& L = lanes[b];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const int n = n0 + r;
+        if (n >= V) break;
+        float v = rbf(acc[b][r]);
+        if (lane == 0) logits[(size_t)b * ldl + n] = v;
+        if (L.seen && L.seen[n]) v = v < 0.f ? v * L.penalty : v / L.penalty;
+        for (int s = 0; s < L.n_suppress; ++s)
+          if (suppress[s] == n) v = -INFINITY;
+        if (v > best[b] || (v == best[b] && n < bi[b])) { best[b] = v; bi[b] = n; }
+      }
+    }
+  }
+  __shared__ float sb[NB][4];
+  __shared__ int si[NB][4];
+  if (lane == 0) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) { sb[b][wave] = best[b]; si[b][wave] = bi[b]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < NB && lane_live(lanes[threadIdx.x])) {
+    const int b = threadIdx.x;
+    float bb = sb[b][0];
+    int ii = si[b][0];
+    for (int w = 1; w < 4; ++w)
+      if (sb[b][w] > bb || (sb[b][w] == bb && si[b][w] < ii)) { bb = sb[b][w]; ii = si[b][w]; }
+    float* pv = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (size_t)b * ws_stride);
+    int* pi = reinterpret_cast<int*>(pv + gridDim.x);
+    pv[blockIdx.x] = bb;
+    pi[blockIdx.x] = ii;
+  }
+}
+
+__global__ __launch_bounds__(1024) void decb_argmax_finish_kernel(const svlm_lane* __restrict__ lanes, const float* __restrict__ ws,
+                                                                  long long ws_stride, int n_parts, int advance_kv) {
+  const svlm_lane& L = lanes[blockIdx.x];
+  if (!lane_live(L)) return;
+  const float* pv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ws) + (size_t)blockIdx.x * ws_stride);
+  argmax_finish_body(pv, reinterpret_cast<const int*>(pv + n_parts), n_parts, L.seen, L.tok_buf, L.state, advance_kv);
+}
+
+// ---------------------------------------------------------------- residual GEMVs (o_proj, down_proj)
+// y[b][n] = bf16(bf16(W[n] . x[b]) + residual[b][n]); `y` may be `residual` (in place).  Per (lane, row) the loop of gemv_bf16_kernel.
+template <int NB, int ROWS>
+__global__ __launch_bounds__(256) void decb_gemv_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                        const bf16_t* __restrict__ W, int ldw, const bf16_t* residual, int ldr, bf16_t* y,
+                                                        int ldy, int N, int K) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
+  if (n0 >= N) return;
+  const bf16_t* wr[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, N - 1) * ldw;
+  bool live[NB];
+  float acc[NB][ROWS];
+  bf16_t epi_raw[NB][ROWS];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    live[b] = lane_live(lanes[b]);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      acc[b][r] = 0.f;
+      epi_raw[b][r] = residual[(size_t)b * ldr + min(n0 + r, N - 1)];
+    }
+  }
+  constexpr int PRE = 4;
+  for (int base = 0; base < K; base += PRE * 512) {
+    u32x4_t xv[PRE][NB], wv[PRE][ROWS];
+#pragma unroll
+    for (int it = 0; it < PRE; ++it) {
+      const int c = base + it * 512 + lane * 8;
+      const int cc = c < K ? c : 0;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) xv[it][b] = *reinterpret_cast<const u32x4_t*>(x + (size_t)b * ldx + cc);
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) wv[it][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr[r] + cc));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int it = 0; it < PRE; ++it) {
+      const int c = base + it * 512 + lane * 8;
+      float wf[ROWS][8];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) unpack8(wv[it][r], wf[r]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float xf[8];
+        unpack8(xv[it][b], xf);
+        if (c >= K) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) xf[i] = 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[b][r] = fmaf(wf[r][i], xf[i], acc[b][r]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) acc[b][r] = wave_sum(acc[b][r]);
+  if (lane == 0) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (!live[b]) continue;
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const int n = n0 + r;
+        if (n >= N) break;
+        float v = acc[b][r] + 0.f;                       // (the single-row kernel's "+ no bias": -0 becomes +0 there too)
+        v = rbf(v);
+        v = rbf(v + bf2f(epi_raw[b][r]));
+        y[(size_t)b * ldy + n] = f2bf(v);
+      }
+    }
+  }
+}
+
+// Long-K form (down_proj): the 4 waves of a workgroup take a quarter of K each for the same ROWS rows, as gemv_bf16_ksplit_kernel;
+// the quarters are summed in the same order.
+template <int NB, int ROWS>
+__global__ __launch_bounds__(256) void decb_gemv_ksplit_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                               const bf16_t* __restrict__ W, int ldw, const bf16_t* residual, int ldr,
+                                                               bf16_t* y, int ldy, int N, int K) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * ROWS;
+  const int kq = ((K / 8 + 3) / 4) * 8;
+  const int k_lo = wave * kq, k_hi = min(K, k_lo + kq);
+  const bf16_t* wr[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, N - 1) * ldw;
+  float acc[NB][ROWS];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) acc[b][r] = 0.f;
+  // thread t < NB * ROWS finishes (lane t / ROWS, row t % ROWS); its residual is requested up front
+  const int eb = min((int)threadIdx.x / ROWS, NB - 1), er = threadIdx.x % ROWS;
+  const bf16_t epi_raw = residual[(size_t)eb * ldr + min(n0 + er, N - 1)];
+  constexpr int PRE = 4;
+  for (int base = k_lo; base < k_hi; base += PRE * 512) {
+    u32x4_t xv[PRE][NB], wv[PRE][ROWS];
+#pragma unroll
+    for (int it = 0; it < PRE; ++it) {
+      const int c = base + it * 512 + lane * 8;
+      const int cc = c < k_hi ? c : k_lo;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) xv[it][b] = *reinterpret_cast<const u32x4_t*>(x + (size_t)b * ldx + cc);
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) wv[it][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr[r] + cc));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int it = 0; it < PRE; ++it) {
+      const int c = base + it * 512 + lane * 8;
+      float wf[ROWS][8];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) unpack8(wv[it][r], wf[r]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float xf[8];
+        unpack8(xv[it][b], xf);
+        if (c >= k_hi) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) xf[i] = 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[b][r] = fmaf(wf[r][i], xf[i], acc[b][r]);
+        }
+      }
+    }
+  }
+  __shared__ float part[4][NB][ROWS];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const float s = wave_sum(acc[b][r]);
+      if (lane == 0) part[wave][b][r] = s;
+    }
+  __syncthreads();
+  if (threadIdx.x < NB * ROWS) {
+    const int n = n0 + er;
+    if (n < N && lane_live(lanes[eb])) {
+      float v = part[0][eb][er] + part[1][eb][er] + part[2][eb][er] + part[3][eb][er] + 0.f;
+      v = rbf(v);
+      v = rbf(v + bf2f(epi_raw));
+      y[(size_t)eb * ldy + n] = f2bf(v);
+    }
+  }
+}
+
+// ================================================================ launchers
+// the NB staged rows share the 64 KB of dynamic LDS a launch gets without opting in
+static inline bool decb_ok(int B, int K, int ldx) { return B >= 1 && B <= 4 && K > 0 && K % 8 == 0 && K <= 8192 && B * K * 2 <= 65536 && ldx >= K && ldx % 8 == 0; }
+
+#define DECB_K(KERNEL, NB, K, ...)                                          \
+  do {                                                                      \
+    if ((K) <= 1536) KERNEL<NB, 3, 1> __VA_ARGS__;                          \
+    else if ((K) <= 2048) KERNEL<NB, 4, 1> __VA_ARGS__;                     \
+    else if ((K) <= 4096) KERNEL<NB, 4, 2> __VA_ARGS__;                     \
+    else KERNEL<NB, 4, 4> __VA_ARGS__;                                      \
+  } while (0)
+#define DECB_DISPATCH(KERNEL, B, K, ...)                                    \
+  do {                                                                      \
+    if ((B) == 1) DECB_K(KERNEL, 1, K, __VA_ARGS__);                        \
+    else if ((B) == 2) DECB_K(KERNEL, 2, K, __VA_ARGS__);                   \
+    else if ((B) == 3) DECB_K(KERNEL, 3, K, __VA_ARGS__);                   \
+    else DECB_K(KERNEL, 4, K, __VA_ARGS__);                                 \
+  } while (0)
+#define DECB_ROWS(KERNEL, B, ROWS, ...)                                     \
+  do {                                                                      \
+    if ((B) == 1) KERNEL<1, ROWS> __VA_ARGS__;                              \
+    else if ((B) == 2) KERNEL<2, ROWS> __VA_ARGS__;                         \
+    else if ((B) == 3) KERNEL<3, ROWS> __VA_ARGS__;                         \
+    else KERNEL<4, ROWS> __VA_ARGS__;                                       \
+  } while (0)
+
+extern "C" int svlm_decb_embed(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && B >= 1 && B <= 4 && n_rows > 0 && cols > 0 && cols % 8 == 0 && ldx >= cols && ldx % 8 == 0,
+                 "svlm_decb_embed: bad B=%d n_rows=%d cols=%d ldx=%d", B, n_rows, cols, ldx);
+  decb_embed_kernel<<<dim3((cols / 8 + 255) / 256, B), 256, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const bf16_t*)table,
+                                                                                      (bf16_t*)x, ldx, cols, n_rows);
+  return svlm_check_launch("svlm_decb_embed");
+}
+
+extern "C" int svlm_decb_qkv(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw,
+                             const void* bias, void* q_out, int ldq, int layer, int K, int qd, int kd, int D, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && decb_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0, "svlm_decb_qkv: bad B=%d K=%d ldx=%d ldw=%d", B, K, ldx, ldw);
+  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D == 128 && kd % D == 0 && bias != nullptr && ldq >= qd && layer >= 0,
+                 "svlm_decb_qkv: bad qd=%d kd=%d D=%d ldq=%d layer=%d (head_dim 128)", qd, kd, D, ldq, layer);
+  const int N = qd + 2 * kd;
+  DECB_DISPATCH(decb_qkv_kernel, B, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, (const bf16_t*)bias, (bf16_t*)q_out, ldq,
+      layer, N, K, qd, kd, D));
+  return svlm_check_launch("svlm_decb_qkv");
+}
+
+extern "C" int svlm_decb_gate_up(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw,
+                                 void* h, int ldh, int I, int K, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && decb_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0 && I > 0 && ldh >= I,
+                 "svlm_decb_gate_up: bad B=%d I=%d K=%d ldx=%d ldw=%d ldh=%d", B, I, K, ldx, ldw, ldh);
+  DECB_DISPATCH(decb_gate_up_kernel, B, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, (bf16_t*)h, ldh, I, K));
+  return svlm_check_launch("svlm_decb_gate_up");
+}
+
+extern "C" int svlm_decb_gemv(const void* lanes, int B, const void* x, int ldx, const void* W, int ldw, const void* residual, int ldr,
+                              void* y, int ldy, int N, int K, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && B >= 1 && B <= 4 && N > 0 && K > 0 && K % 8 == 0 && ldw % 8 == 0 && ldw >= K && ldx >= K && ldx % 8 == 0,
+                 "svlm_decb_gemv: bad shape B=%d N=%d K=%d ldw=%d ldx=%d", B, N, K, ldw, ldx);
+  SVLM_CHECK_ARG(residual != nullptr && y != nullptr && ldr >= N && ldy >= N, "svlm_decb_gemv: residual and y are required (ldr=%d ldy=%d)", ldr, ldy);
+  hipStream_t s = (hipStream_t)stream;
+  if (N <= 8192 && K >= 4096) {        // the shapes svlm_gemv_bf16 splits over K
+    DECB_ROWS(decb_gemv_ksplit_kernel, B, 2, <<<(N + 1) / 2, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
+                                                                        (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K));
+    return svlm_check_launch("svlm_decb_gemv(ksplit)");
+  }
+  if (N >= 4096 || (long long)N * K >= (8LL << 20)) {
+    DECB_ROWS(decb_gemv_kernel, B, 2, <<<(N + 7) / 8, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
+                                                                 (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K));
+  } else {
+    DECB_ROWS(decb_gemv_kernel, B, 1, <<<(N + 3) / 4, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
+                                                                 (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K));
+  }
+  return svlm_check_launch("svlm_decb_gemv");
+}
+
+extern "C" long long svlm_decb_lm_head_ws_stride(int V) {
+  if (V <= 0) return SVLM_EINVAL;
+  const long long nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
+  return (nb * 8 + 15) / 16 * 16;
+}
+
+extern "C" int svlm_decb_lm_head(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw,
+                                 float* logits, int ldl, const int* suppress, void* ws, int V, int K, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && decb_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0 && V > 0 && ldl >= V,
+                 "svlm_decb_lm_head: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d", B, V, K, ldx, ldw, ldl);
+  SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head: null logits / workspace");
+  const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
+  DECB_DISPATCH(decb_lm_head_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, logits, ldl, suppress, (float*)ws,
+      svlm_decb_lm_head_ws_stride(V), V, K));
+  return svlm_check_launch("svlm_decb_lm_head");
+}
+
+extern "C" int svlm_decb_argmax_finish(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && B >= 1 && B <= 4 && V > 0 && ws != nullptr, "svlm_decb_argmax_finish: bad args");
+  const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
+  decb_argmax_finish_kernel<<<B, 1024, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const float*)ws, svlm_decb_lm_head_ws_stride(V), nb,
+                                                                 advance_kv);
+  return svlm_check_launch("svlm_decb_argmax_finish");
+}

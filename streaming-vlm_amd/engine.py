@@ -17,6 +17,7 @@ import math
 import os
 import weakref
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -247,7 +248,14 @@ class SvlmEngine:
     def __init__(self, cfg: ModelConfig, state_dict, device="cuda", ops=None, max_len: int = 4096, max_new_tokens: int = 32,
                  decode_chunk: Optional[int] = None, use_graph: Optional[bool] = None, kv_slack: float = 1.0, kv_page_tokens: int = 16,
                  decode_tail: Optional[bool] = None,
-                 vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False):
+                 vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None):
+        """`share`: another engine of the same model whose WEIGHTS this one uses (language model, vision tower, embedding, lm_head,
+        rope frequencies, fp8 vision images): `state_dict` is ignored and no weight tensor is copied; every per-stream buffer (sampling
+        state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py)."""
+        if share is not None:
+            if share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8:
+                raise ValueError("share=: the engines must agree on model config, device, llm_fp8 and vit_fp8")
+            ops = share.ops if ops is None else ops
         if ops is None:
             from .ops import HipOps
             ops = HipOps()                      # raises when the HIP extension / GPU is missing
@@ -267,14 +275,16 @@ class SvlmEngine:
                 raise ValueError(f"llm_fp8=True needs an ops backend with the fp8 entry points; {type(ops).__name__} lacks {missing}")
             if decode_tail or (decode_tail is None and os.environ.get("SVLM_DECODE_TAIL", "0") == "1"):
                 raise ValueError("llm_fp8=True cannot be combined with decode_tail=True (the persistent layer tail streams bf16 weights)")
-        self.w = EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8)
+        self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8)
         self._fp8_scratch = None           # llm_fp8: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
         tc, vc = cfg.text, cfg.vision
         if tc.head_dim != 128 or sum(tc.mrope_section) * 2 != tc.head_dim:
             raise ValueError("LLM head_dim must be 128 with mrope sections summing to 64")
         # BASELINE configs[4]: the vision tower's Linears on the fp8 MFMA path (svlm_gemm_fp8), weights quantised once here
         self.vit_fp8 = bool(vit_fp8)
-        if self.vit_fp8:
+        if self.vit_fp8 and share is not None:
+            self.vit_w8 = share.vit_w8
+        elif self.vit_fp8:
             if vc.arch != "qwen2" or vc.embed_dim % 128 or vc.mlp_hidden % 128:
                 raise ValueError("vit_fp8 needs the Qwen2-VL tower with widths that are multiples of 128 (LiveCC-7B / Qwen2-VL)")
 
@@ -300,7 +310,7 @@ class SvlmEngine:
         self.qd, self.kd = tc.num_heads * tc.head_dim, tc.num_kv_heads * tc.head_dim
         # rope: inv_freq exactly as Qwen2VLRotaryEmbedding computes it (fp32, host)
         inv = 1.0 / (tc.rope_theta ** (torch.arange(0, tc.head_dim, 2, dtype=torch.float) / tc.head_dim))
-        self.inv_freq = inv.to(dev)
+        self.inv_freq = share.inv_freq if share is not None else inv.to(dev)
         self.pos3_dev = torch.zeros((3, self.max_len), dtype=torch.int32, device=dev)
         self.posf_dev = torch.zeros((3, self.max_len), dtype=torch.float32, device=dev) if cfg.family == "qwen2_5" else None
         self.rope_cs = torch.zeros((self.max_len, tc.head_dim), dtype=BF16, device=dev)
@@ -720,7 +730,25 @@ class SvlmEngine:
         encoded on a side stream underneath this chunk's decode steps (see `vision_prefetch`).
         `force_tokens` (greedy only): teacher forcing for parity tests -- every step still takes its own argmax on the device
         (returned in `.own`), then the given token is fed back instead, so that the logits of EVERY forward can be compared
-        with a reference even after a near-tie went the other way."""
+        with a reference even after a near-tie went the other way.
+        The call is its three phases in order; a stream group (stream_group.py) runs `generate_begin` and `generate_finish` per lane
+        around its own lock-step decode loop."""
+        ctx = self.generate_begin(ids, cache, video_grid_thw, pixel_values=pixel_values, grid_thw=grid_thw, max_new_tokens=max_new_tokens,
+                                  repetition_penalty=repetition_penalty, do_sample=do_sample, temperature=temperature, suppress_eos=suppress_eos,
+                                  keep_logits=keep_logits, generator=generator, next_vision=next_vision, all_text=all_text,
+                                  second_per_grid_t=second_per_grid_t, pos_mode=pos_mode, last_cache_position=last_cache_position,
+                                  force_tokens=force_tokens, top_k=top_k, top_p=top_p)
+        self.generate_steps(ctx)
+        return self.generate_finish(ctx)
+
+    def generate_begin(self, ids: Sequence[int], cache: Optional[KVPool], video_grid_thw, pixel_values=None, grid_thw=None,
+                       max_new_tokens: int = 20, repetition_penalty: float = 1.05, do_sample: bool = False, temperature: float = 1.0,
+                       suppress_eos: bool = False, keep_logits: bool = False, generator=None, next_vision=None,
+                       all_text: bool = False, second_per_grid_t: Optional[float] = None, pos_mode: str = "shrink",
+                       last_cache_position: float = -1, force_tokens: Optional[Sequence[int]] = None, top_k: Optional[int] = None,
+                       top_p: Optional[float] = None):
+        """Phase 1 of `generate`: validation, positions, rope table, slot reservation, ViT, prefill passes, first token.  Returns the
+        call's context for `generate_steps` / `generate_finish`."""
         cfg, tc, o = self.cfg, self.cfg.text, self.ops
         ids = np.asarray(ids, dtype=np.int64).reshape(-1)
         if cache is None:
@@ -867,7 +895,17 @@ class SvlmEngine:
         if next_vision is not None and self.device.type == "cuda":
             ev_pre = torch.cuda.Event()
             ev_pre.record()                 # the look-ahead ViT may start here: behind the prefill, beside the decode steps
-        eos_poll = 0 if (suppress_eos or self.device.type != "cuda") else 4
+        return SimpleNamespace(ids=ids, cache=cache, L_before=L_before, L_ids=L_ids, max_new_tokens=max_new_tokens, suppress_eos=suppress_eos,
+                               keep_logits=keep_logits, logits_out=logits_out, own=own, force_tokens=force_tokens,
+                               seen_host=seen_host if own is not None else None, next_vision=next_vision, ev_pre=ev_pre, on_device=on_device,
+                               pos_full=pos_full, prefetched=False)
+
+    def generate_steps(self, ctx) -> None:
+        """Phase 2 of `generate`: the decode steps of one stream (token 1 .. max_new_tokens - 1), with the one-poll-behind EOS look."""
+        cfg = self.cfg
+        cache, max_new_tokens, keep_logits, logits_out, own = ctx.cache, ctx.max_new_tokens, ctx.keep_logits, ctx.logits_out, ctx.own
+        force_tokens, seen_host, next_vision, ev_pre = ctx.force_tokens, ctx.seen_host, ctx.next_vision, ctx.ev_pre
+        eos_poll = 0 if (ctx.suppress_eos or self.device.type != "cuda") else 4
         poll, prefetched = None, False       # poll: (event, host buffer, token count) of the look that is still in flight
         for step in range(1, max_new_tokens):
             self._decode_step(cache)
@@ -893,6 +931,14 @@ class SvlmEngine:
                 self._poll_host[k][:step + 1].copy_(self.tok_buf[:step + 1], non_blocking=True)
                 self._poll_ev[k].record()
                 poll = (self._poll_ev[k], self._poll_host[k], step + 1)
+        ctx.prefetched = prefetched
+
+    def generate_finish(self, ctx) -> GenerateOutput:
+        """Phase 3 of `generate`: token copy-out (the chunk's one host sync), EOS scan, `cache.commit`, positions bookkeeping."""
+        cfg = self.cfg
+        ids, cache, L_before, L_ids, max_new_tokens = ctx.ids, ctx.cache, ctx.L_before, ctx.L_ids, ctx.max_new_tokens
+        on_device, pos_full, logits_out, own = ctx.on_device, ctx.pos_full, ctx.logits_out, ctx.own
+        next_vision, ev_pre, prefetched = ctx.next_vision, ctx.ev_pre, ctx.prefetched
         # the one host sync of the chunk waits for the TOKENS only: the held-back ViT tail of the look-ahead pass is enqueued
         # behind the copy and keeps the GPU busy while the host turns the chunk around
         if self.device.type == "cuda":

@@ -1,6 +1,7 @@
-"""One independent stream per GPU -- the only parallelism the path has (reference:
+"""Parallelism across streams.  Across GPUs: one independent process per GPU (reference:
 eval/livesports3kcc/distributed_generate_streaming.py:55,62,127-143: N processes, `cuda:{rank}`, strided
-sample sharding, results joined outside the model; no data-path communication).
+sample sharding, results joined outside the model; no data-path communication).  On one GPU: a stream group
+(`streaming_inference_group`, stream_group.py): up to 4 streams share one weight set and decode in lock-step.
 
 `torch.distributed` ("nccl" == RCCL over xGMI on ROCm, "gloo" in CPU tests) is used for exactly two things,
 both OUTSIDE the timed region: a barrier on each side of it and one all_gather of three doubles per rank.
@@ -60,6 +61,65 @@ def aggregate(frames: float, tokens: float, seconds: float, dist, device="cpu") 
     t_max = float(allst[:, 2].max())
     return {"frames_per_sec": float(allst[:, 0].sum()) / t_max, "tokens_per_sec": float(allst[:, 1].sum()) / t_max,
             "t_max": t_max, "per_rank_frames_per_sec": (allst[:, 0] / allst[:, 2]).tolist(), "world": allst.shape[0]}
+
+
+# ----------------------------------------------------------------------------- several streams on one GPU
+class StreamGroupError(RuntimeError):
+    """A stream of `streaming_inference_group` raised: `.index` is its position in `streams`, `.results` the per-stream response
+    lists of the streams that completed (None for those that did not); the stream's own exception is the `__cause__`."""
+
+    def __init__(self, index: int, results: List, cause: BaseException):
+        super().__init__(f"stream {index} failed: {type(cause).__name__}: {cause}")
+        self.index, self.results = index, results
+
+
+def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Optional[int] = None, group=None, **common_kw) -> List:
+    """Run `len(streams)` streams on ONE GPU through a stream group: each entry of `streams` holds the per-stream keyword arguments of
+    `streaming_inference` (video_path, query, previous_text, duration, ...), `common_kw` the shared ones.  Every stream runs the
+    unchanged `streaming_inference` loop in its own host thread against its lane's model object; the lanes' generate() calls meet in
+    the group, which runs one batch when every lane that still has a stream has a request pending.  `n_lanes` defaults to min(3, streams): the measured
+    aggregate throughput stops growing there.  More streams than lanes: they are
+    queued, and a lane that finishes a stream takes the next one; a lane with nothing left detaches and the rest carry on.
+    Greedy decoding only (pass do_sample=False, or top_k=1); strict-causal (no look-ahead ViT).  Returns the per-stream response
+    lists in the order of `streams`; if a stream raised, the others still run to their end and a `StreamGroupError` naming the first
+    failed stream's index is raised afterwards."""
+    import threading
+    from .driver import streaming_inference
+    from .stream_group import DEFAULT_LANES, StreamGroup
+    if group is None:
+        group = StreamGroup(model._svlm_engine, min(DEFAULT_LANES, len(streams)) if n_lanes is None else n_lanes)
+    results: List = [None] * len(streams)
+    errors = {}
+    lock = threading.Lock()
+    todo = list(range(len(streams)))
+
+    def lane_thread(i):
+        lane_model = group.lane_model(i)
+        try:
+            while True:
+                with lock:
+                    if not todo:
+                        return
+                    s = todo.pop(0)
+                try:
+                    results[s] = streaming_inference(model=lane_model, processor=processor, **{**common_kw, **streams[s]})
+                except BaseException as e:          # this stream only: the lane goes on to the next one
+                    errors[s] = e
+        finally:
+            group.detach(i)
+
+    n = min(group.n_lanes, len(streams))
+    for i in range(n):
+        group.attach(i)                              # all lanes are attached before any of them can complete a batch alone
+    threads = [threading.Thread(target=lane_thread, args=(i,), name=f"svlm-lane-{i}", daemon=True) for i in range(n)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        first = min(errors)
+        raise StreamGroupError(first, results, errors[first]) from errors[first]
+    return results
 
 
 # ----------------------------------------------------------------------------- sample-sharded generation

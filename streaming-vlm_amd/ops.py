@@ -631,6 +631,94 @@ class HipOps:
         _req(state, torch.int32, "argmax_finish.state", 1)
         check(self.lib.svlm_argmax_finish(_ptr(ws), V, _ptr(seen), _ptr(tok_buf), _ptr(state), int(advance_kv), _stream()), "svlm_argmax_finish")
 
+    # ------------------------------------------------------------------ lane-batched decode step (csrc/decode_batch.hip)
+    LANE_WORDS = 9          # int64 words of one svlm_lane record (include/svlm.h)
+
+    @staticmethod
+    def lane_record(pool, lin, slot_of, state, tok_buf, seen, limit, penalty=1.0, n_suppress=0):
+        """One svlm_lane record as int64[LANE_WORDS] on the host, from the tensors a lane owns (validated here: the kernels trust it)."""
+        import numpy as np
+        _req(pool, BF16, "lane.pool", 5); _req(slot_of, torch.int32, "lane.slot_of", 1); _req(state, torch.int32, "lane.state", 1)
+        _req(tok_buf, torch.int32, "lane.tok_buf", 1)
+        _, two, Hkv, n_slots, D = pool.shape
+        assert two == 2 and pool.is_contiguous() and state.numel() >= 2 and 0 <= int(limit) <= tok_buf.numel(), (tuple(pool.shape), limit)
+        lin_rows = 0
+        if lin is not None:
+            _req(lin, BF16, "lane.lin", 5)
+            assert lin.is_contiguous() and lin.shape[:3] == pool.shape[:3] and lin.shape[4] == D and lin.shape[3] % 16 == 0, tuple(lin.shape)
+            lin_rows = lin.shape[3]
+            assert slot_of.numel() <= lin_rows, (slot_of.numel(), lin_rows)
+        if seen is not None:
+            _req(seen, torch.uint8, "lane.seen", 1)
+        assert float(penalty) > 0 and 0 <= int(n_suppress) <= 8
+        rec = np.zeros(HipOps.LANE_WORDS, dtype=np.int64)
+        rec[:6] = [_ptr(pool), _ptr(lin), _ptr(slot_of), _ptr(state), _ptr(tok_buf), _ptr(seen)]
+        tail = rec[6:].view(np.int32)
+        tail[0], tail[1], tail[2], tail[4] = int(limit), n_slots, lin_rows, int(n_suppress)
+        tail[3:4].view(np.float32)[0] = float(penalty)
+        return rec
+
+    def _lanes(self, lanes, B, what):
+        _req(lanes, torch.int64, what + ".lanes", 2)
+        if not (1 <= B <= 4 and lanes.shape[0] >= B and lanes.shape[1] == self.LANE_WORDS and lanes.is_contiguous()):
+            raise _lib.SvlmError(f"{what}: lane table {tuple(lanes.shape)} for B={B} (1..4 lanes of {self.LANE_WORDS} words)")
+
+    @staticmethod
+    def _rows(t, B, cols, name, dtype=BF16):
+        _req(t, dtype, name, 2)
+        if t.shape[0] < B or t.shape[1] < cols:
+            raise _lib.SvlmError(f"{name}: shape {tuple(t.shape)} cannot hold {B} rows of {cols}")
+        return t.stride(0)
+
+    def decb_embed(self, lanes, B, table, x):
+        self._lanes(lanes, B, "decb_embed"); _req(table, BF16, "decb_embed.table", 2)
+        assert table.is_contiguous()
+        ldx = self._rows(x, B, table.shape[1], "decb_embed.x")
+        check(self.lib.svlm_decb_embed(_ptr(lanes), B, _ptr(table), table.shape[0], _ptr(x), ldx, table.shape[1], _stream()), "svlm_decb_embed")
+
+    def decb_qkv(self, lanes, B, x, ln_w, eps, W, bias, q_out, layer, qd, kd, D, n_layers):
+        self._lanes(lanes, B, "decb_qkv"); _req(ln_w, BF16, "decb_qkv.ln_w", 1); _req(W, BF16, "decb_qkv.W", 2); _req(bias, BF16, "decb_qkv.bias", 1)
+        N, K = W.shape
+        assert N == qd + 2 * kd == bias.numel() and ln_w.numel() == K and 0 <= layer < n_layers
+        ldx, ldq = self._rows(x, B, K, "decb_qkv.x"), self._rows(q_out, B, qd, "decb_qkv.q_out")
+        check(self.lib.svlm_decb_qkv(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(bias), _ptr(q_out), ldq,
+                                     int(layer), K, qd, kd, D, _stream()), "svlm_decb_qkv")
+
+    def decb_gate_up(self, lanes, B, x, ln_w, eps, W, h):
+        self._lanes(lanes, B, "decb_gate_up"); _req(ln_w, BF16, "decb_gate_up.ln_w", 1); _req(W, BF16, "decb_gate_up.W", 2)
+        N, K = W.shape
+        assert N % 2 == 0 and ln_w.numel() == K
+        ldx, ldh = self._rows(x, B, K, "decb_gate_up.x"), self._rows(h, B, N // 2, "decb_gate_up.h")
+        check(self.lib.svlm_decb_gate_up(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(h), ldh, N // 2, K,
+                                         _stream()), "svlm_decb_gate_up")
+
+    def decb_gemv(self, lanes, B, x, W, residual, out):
+        self._lanes(lanes, B, "decb_gemv"); _req(W, BF16, "decb_gemv.W", 2)
+        N, K = W.shape
+        ldx, ldr, ldy = self._rows(x, B, K, "decb_gemv.x"), self._rows(residual, B, N, "decb_gemv.residual"), self._rows(out, B, N, "decb_gemv.out")
+        check(self.lib.svlm_decb_gemv(_ptr(lanes), B, _ptr(x), ldx, _ptr(W), W.stride(0), _ptr(residual), ldr, _ptr(out), ldy, N, K, _stream()),
+              "svlm_decb_gemv")
+
+    def decb_sampling_ws(self, V, B, device):
+        """Candidate workspace of a group: B blocks of svlm_decb_lm_head_ws_stride(V) bytes."""
+        return torch.empty((B, self.lib.svlm_decb_lm_head_ws_stride(V) // 4), dtype=torch.float32, device=device)
+
+    def decb_lm_head(self, lanes, B, x, ln_w, eps, W, logits, suppress, ws):
+        """suppress: int32 list on the device (<= 8 ids); lane b applies its first `n_suppress` entries (lane table)."""
+        self._lanes(lanes, B, "decb_lm_head"); _req(ln_w, BF16, "decb_lm_head.ln_w", 1); _req(W, BF16, "decb_lm_head.W", 2)
+        _req(suppress, torch.int32, "decb_lm_head.suppress", 1); _req(ws, torch.float32, "decb_lm_head.ws", 2)
+        V, K = W.shape
+        assert ln_w.numel() == K and suppress.numel() >= 8 and ws.is_contiguous()
+        assert ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        ldx, ldl = self._rows(x, B, K, "decb_lm_head.x"), self._rows(logits, B, V, "decb_lm_head.logits", torch.float32)
+        check(self.lib.svlm_decb_lm_head(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), ldl,
+                                         _ptr(suppress), _ptr(ws), V, K, _stream()), "svlm_decb_lm_head")
+
+    def decb_argmax_finish(self, lanes, B, ws, V, advance_kv):
+        self._lanes(lanes, B, "decb_argmax_finish"); _req(ws, torch.float32, "decb_argmax_finish.ws", 2)
+        assert ws.is_contiguous() and ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        check(self.lib.svlm_decb_argmax_finish(_ptr(lanes), B, _ptr(ws), V, int(advance_kv), _stream()), "svlm_decb_argmax_finish")
+
     # ------------------------------------------------------------------ fp8 language-model weights (csrc/decode_fp8.hip)
     @staticmethod
     def _req_fp8(W8, scale, name):

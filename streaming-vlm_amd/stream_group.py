@@ -1,0 +1,299 @@
+"""Stream groups: B independent streams (B = 1..4, "lanes") on one GPU and ONE weight set, whose decode steps run in lock-step through
+the lane-batched kernels of csrc/decode_batch.hip -- each weight byte is read once and each launch boundary paid once for B tokens.
+
+A lane is an `SvlmEngine` that shares the group engine's weights (`SvlmEngine(share=...)`; lane 0 IS the group engine) and owns
+everything a stream owns: KV pool, positions, rope table, sampling state, eviction history.  `StreamGroup.generate` runs
+`generate_begin` lane after lane (the prefill stays per stream), then the lock-step batched decode steps, then `generate_finish` per
+lane; per lane the tokens, cache length and logical order are EXACTLY those of the stream run alone (the batched kernels are bitwise
+the single-row ones per lane, and the decode attention is the unchanged single-stream kernel, launched once per lane).
+
+Opt-in; nothing here is reached by the single-stream path.  Refused with a ValueError instead of silently falling back:
+`llm_fp8=True` and `decode_tail=True` engines, `do_sample=True` with anything but `top_k == 1`, `force_tokens`, `keep_logits`.
+The look-ahead ViT (`next_vision`) is DECLINED: a group runs strict-causal, every chunk's vision tower runs inside its own
+`generate_begin`.
+"""
+from __future__ import annotations
+
+import inspect
+import math
+import threading
+import time
+import weakref
+from types import MethodType
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .engine import BF16, GenerateOutput, SvlmEngine
+
+MAX_LANES = 4
+# aggregate frames/s stops growing at 3 lanes on Qwen2-VL-2B (profiles/stream_group_2b.json: 4 lanes are 0.6 % below 3), so nothing picks
+# more than 3 by itself; 4 remain available on request
+DEFAULT_LANES = 3
+
+
+def check_request(req: dict) -> dict:
+    """Validate one lane's request (the keyword arguments of `SvlmEngine.generate`); returns it without the declined `next_vision`."""
+    req = dict(req)
+    req.pop("next_vision", None)
+    if req.get("force_tokens") is not None:
+        raise ValueError("stream group: force_tokens (teacher forcing) is a single-stream parity aid and is not supported")
+    if req.get("keep_logits"):
+        raise ValueError("stream group: keep_logits is not supported (the per-step logits of a lane stay on the device)")
+    if req.get("do_sample") and req.get("top_k") != 1:
+        raise ValueError("stream group: only greedy decoding is batched; do_sample=True needs top_k=1 "
+                         f"(got top_k={req.get('top_k')!r}, top_p={req.get('top_p')!r})")
+    return req
+
+
+class LaneRendezvous:
+    """Host-side rendezvous of the lanes' threads.  A lane thread `attach`es, then calls `submit(i, request)` per chunk and blocks;
+    the batch runs when EVERY attached lane has a request pending, on the thread whose arrival (or whose neighbour's `detach`)
+    completed it -- all GPU work of a batch is issued from that one thread.  `run_batch(requests)` gets one request or None per
+    lane and returns one result per lane; a result that is an exception is raised in that lane's `submit` only."""
+
+    def __init__(self, n_lanes: int, run_batch: Callable[[List[Optional[dict]]], Sequence]):
+        self.n_lanes = int(n_lanes)
+        self._run = run_batch
+        self._cv = threading.Condition()
+        self._attached, self._pending, self._results = set(), {}, {}
+        self._running = False
+        self.batches = 0
+
+    def attach(self, i: int) -> None:
+        with self._cv:
+            if not 0 <= i < self.n_lanes or i in self._attached:
+                raise ValueError(f"lane {i} is out of range or already attached")
+            self._attached.add(i)
+
+    def detach(self, i: int) -> None:
+        """The lane's stream has ended (or raised): the others carry on with a smaller batch."""
+        with self._cv:
+            self._attached.discard(i)
+            self._pending.pop(i, None)
+            self._cv.notify_all()
+
+    def submit(self, i: int, request: dict, timeout: Optional[float] = None):
+        deadline = None if timeout is None else time.monotonic() + timeout
+        with self._cv:
+            if i not in self._attached or i in self._pending:
+                raise RuntimeError(f"lane {i} is not attached or already has a request pending")
+            self._pending[i] = request
+            while True:
+                if i in self._results:
+                    out = self._results.pop(i)
+                    if isinstance(out, BaseException):
+                        raise out
+                    return out
+                if not self._running and i in self._pending and self._attached <= self._pending.keys():
+                    batch, self._pending = self._pending, {}
+                    self._running = True
+                    self._cv.release()
+                    try:
+                        try:
+                            out = list(self._run([batch.get(k) for k in range(self.n_lanes)]))
+                        except BaseException as e:       # the batch as a whole failed: every lane of it hears about it
+                            out = [e] * self.n_lanes
+                    finally:
+                        self._cv.acquire()
+                    for k in batch:
+                        self._results[k] = out[k]
+                    self._running = False
+                    self.batches += 1
+                    self._cv.notify_all()
+                    continue
+                left = None if deadline is None else deadline - time.monotonic()
+                if left is not None and left <= 0:
+                    self._pending.pop(i, None)
+                    raise TimeoutError(f"lane {i}: no batch within {timeout} s")
+                self._cv.wait(left)
+
+
+class _LaneEngine:
+    """What a lane model shows as `_svlm_engine`: the lane's engine, with `generate` handed to the group."""
+
+    _SIG = inspect.signature(SvlmEngine.generate)
+
+    def __init__(self, group: "StreamGroup", i: int):
+        self._group, self._i, self._eng = group, i, group.lanes[i]
+
+    def __getattr__(self, name):
+        return getattr(self._eng, name)
+
+    def generate(self, *args, **kw) -> GenerateOutput:
+        req = dict(self._SIG.bind(None, *args, **kw).arguments)
+        req.pop("self")
+        return self._group.submit(self._i, req)
+
+
+class LaneModel:
+    """The surface `streaming_inference` uses of a model (`.config`, `.device`, `._svlm_engine`, `.generate`, `.new_cache`) for one
+    lane: `generate` hands its request to the group and waits for the batch."""
+
+    def __init__(self, group: "StreamGroup", i: int):
+        from .model import streaming_generate
+        self.config = group.lanes[i].cfg
+        self.device = group.lanes[i].device
+        self._svlm_engine = _LaneEngine(group, i)
+        self.generate = MethodType(streaming_generate, self)
+
+    def new_cache(self):
+        return self._svlm_engine.new_cache()
+
+
+class StreamGroup:
+    def __init__(self, engine: SvlmEngine, n_lanes: int = 2):
+        if not 1 <= int(n_lanes) <= MAX_LANES:
+            raise ValueError(f"n_lanes={n_lanes} outside [1, {MAX_LANES}]")
+        if getattr(engine, "llm_fp8", False):
+            raise ValueError("stream group: llm_fp8=True engines are not supported (the lane-batched kernels stream bf16 weights)")
+        if getattr(engine, "decode_tail", False):
+            raise ValueError("stream group: decode_tail=True engines are not supported (the persistent layer tail is single-row)")
+        self.engine = engine
+        self.n_lanes = int(n_lanes)
+        tc, dev, o = engine.cfg.text, engine.device, engine.ops
+        self.lanes: List[SvlmEngine] = [engine] + [
+            SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
+                       use_graph=engine.use_graph, kv_slack=engine.kv_slack, kv_page_tokens=engine.kv_page_tokens, decode_tail=False,
+                       vit_fp8=engine.vit_fp8, linear_planes=engine.linear_planes, share=engine) for _ in range(self.n_lanes - 1)]
+        for ln in self.lanes[1:]:
+            ln.default_top_k, ln.default_top_p, ln.eos_dev = engine.default_top_k, engine.default_top_p, engine.eos_dev
+        B, H, V = self.n_lanes, tc.hidden_size, tc.vocab_size
+        self.use_graph = engine.use_graph
+        # group-owned activations of the batched step, one row per live lane of the batch
+        self.x = torch.zeros((B, H), dtype=BF16, device=dev)
+        self.q = torch.zeros((B, engine.qd), dtype=BF16, device=dev)
+        self.attn = torch.zeros((B, engine.qd), dtype=BF16, device=dev)
+        self.h = torch.zeros((B, tc.intermediate_size), dtype=BF16, device=dev)
+        self.logits = torch.zeros((B, V), dtype=torch.float32, device=dev)
+        self.ws = o.decb_sampling_ws(V, B, dev)
+        eos = list(engine.cfg.eos_token_ids)
+        if len(eos) > 8:
+            raise ValueError("stream group: at most 8 EOS ids can be suppressed")
+        self.suppress = torch.tensor(eos + [-1] * (8 - len(eos)), dtype=torch.int32, device=dev)
+        # the lane table (svlm_lane records): rows [0, B) are the batch, written at the start of every generate(); a lane parked by an
+        # EOS look gets its row rewritten (limit 0) from the second half of the page-locked staging block
+        W = o.LANE_WORDS
+        self.table = torch.zeros((B, W), dtype=torch.int64, device=dev)
+        self._table_host = torch.zeros((2 * B, W), dtype=torch.int64)
+        if dev.type == "cuda":
+            self._table_host = self._table_host.pin_memory()
+        self._graphs = {}
+        self.max_graphs = engine.max_graphs
+        self._rv = LaneRendezvous(self.n_lanes, lambda reqs: self.generate(reqs, return_exceptions=True))
+        self.attach, self.detach, self.submit = self._rv.attach, self._rv.detach, self._rv.submit
+
+    def lane_model(self, i: int) -> LaneModel:
+        return LaneModel(self, i)
+
+    # ------------------------------------------------------------------ lane table
+    def _record(self, lane: SvlmEngine, cache, limit: int):
+        lin = cache.lin_args() if hasattr(cache, "lin_args") else None
+        return self.engine.ops.lane_record(cache.pool, None if lin is None else lin[0], cache.slot_of_dev, lane.state, lane.tok_buf,
+                                           lane.seen if lane._penalty != 1.0 else None, limit, lane._penalty,
+                                           len(self.engine.cfg.eos_token_ids) if lane._suppress is not None else 0)
+
+    def _write_row(self, row: int, rec: np.ndarray, stage_row: int):
+        self._table_host[stage_row].copy_(torch.from_numpy(rec))
+        self.table[row].copy_(self._table_host[stage_row], non_blocking=True)
+
+    # ------------------------------------------------------------------ one batched decode step
+    def _step_launch(self, act):
+        """One token for every live lane of the batch: per layer [norm+QKV+append]xB-in-one, B x [attn split, attn combine],
+        [o+res]xB-in-one, [norm+gate/up+SwiGLU]xB-in-one, [down+res]xB-in-one; then the head and the token feedback."""
+        e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
+        B, qd, kd, nl = len(act), e.qd, e.kd, len(self.engine.w.layers)
+        scale = 1.0 / math.sqrt(tc.head_dim)
+        tab = self.table
+        o.decb_embed(tab, B, w.embed, self.x)
+        for li, lw in enumerate(w.layers):
+            o.decb_qkv(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
+            for j, (lane, c) in enumerate(act):          # the single-stream attention, once per lane, same stream (no forked branches)
+                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
+                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            o.decb_gemv(tab, B, self.attn, lw["o_w"], self.x, self.x)
+            o.decb_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
+            o.decb_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
+        o.decb_lm_head(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
+        o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
+
+    def _step(self, idx, act):
+        if not self.use_graph:
+            self._step_launch(act)
+            return
+        # keyed on the lanes of the batch, their caches and attention geometry; penalty / suppression / limits live in the lane table
+        key = tuple((i, c.serial, lane.decode_chunk, lane._attn_len) for i, (lane, c) in zip(idx, act))
+        hit = self._graphs.get(key)
+        if hit is not None and any(r() is not c for r, (_, c) in zip(hit[1], act)):
+            hit = None
+        if hit is None:
+            g = torch.cuda.CUDAGraph()
+            # thread-local capture: other lanes' host threads may be preparing their next chunk (frame ingest) meanwhile
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._step_launch(act)
+            for k in [k for k, v in self._graphs.items() if any(r() is None for r in v[1])]:
+                del self._graphs[k]          # graphs of pools that are gone (a graph must not keep its pools alive)
+            if len(self._graphs) >= self.max_graphs:
+                self._graphs.pop(next(iter(self._graphs)))
+            hit = self._graphs[key] = (g, [weakref.ref(c) for _, c in act])
+        hit[0].replay()
+
+    # ------------------------------------------------------------------ generate
+    def generate(self, requests: Sequence[Optional[dict]], return_exceptions: bool = False) -> List:
+        """One request (keyword arguments of `SvlmEngine.generate`: ids, cache, video_grid_thw, ...) or None per lane -> one
+        `GenerateOutput` or None per lane.  `return_exceptions`: a lane whose request is refused or whose begin / finish raises gets
+        the exception object as its result and the other lanes carry on (default: the first such exception is raised)."""
+        if len(requests) != self.n_lanes:
+            raise ValueError(f"{len(requests)} requests for {self.n_lanes} lanes")
+        out: List = [None] * self.n_lanes
+        idx, act, ctxs = [], [], []
+        for i, req in enumerate(requests):
+            if req is None:
+                continue
+            try:
+                ctx = self.lanes[i].generate_begin(**check_request(req))
+            except Exception as e:
+                if not return_exceptions:
+                    raise
+                out[i] = e
+                continue
+            idx.append(i)
+            act.append((self.lanes[i], ctx.cache))
+            ctxs.append(ctx)
+        B = len(act)
+        dev_is_gpu = self.engine.device.type == "cuda"
+        if B:
+            for j, ((lane, c), ctx) in enumerate(zip(act, ctxs)):
+                self._write_row(j, self._record(lane, c, ctx.max_new_tokens), j)
+            n_steps = max(ctx.max_new_tokens for ctx in ctxs) - 1
+            done = [False] * B                   # host view: an EOS was seen among the lane's tokens
+            polls = [None] * B                   # per lane: (event, host buffer, token count) of the look still in flight
+            for step in range(1, n_steps + 1):
+                if not any(step < ctx.max_new_tokens and not done[j] for j, ctx in enumerate(ctxs)):
+                    break                        # no lane is live: nothing more to launch
+                self._step(idx, act)
+                # the single stream's one-poll-behind EOS look, per lane (engine.generate_steps): a lane whose tokens show an EOS is
+                # parked (limit 0 in its table row) for the steps not yet queued; its rows past the EOS are rolled back by its commit
+                if dev_is_gpu and step % 4 == 0 and step + 1 < n_steps + 1:
+                    for j, ((lane, c), ctx) in enumerate(zip(act, ctxs)):
+                        if ctx.suppress_eos or done[j] or step + 1 >= ctx.max_new_tokens:
+                            continue
+                        if polls[j] is not None:
+                            polls[j][0].synchronize()
+                            if any(int(t) in self.engine.cfg.eos_token_ids for t in polls[j][1][:polls[j][2]].tolist()):
+                                done[j] = True
+                                self._write_row(j, self._record(lane, c, 0), self.n_lanes + j)
+                                continue
+                        k = (step // 4) & 1
+                        lane._poll_host[k][:step + 1].copy_(lane.tok_buf[:step + 1], non_blocking=True)
+                        lane._poll_ev[k].record()
+                        polls[j] = (lane._poll_ev[k], lane._poll_host[k], step + 1)
+        for i, (lane, _), ctx in zip(idx, act, ctxs):
+            try:
+                out[i] = lane.generate_finish(ctx)
+            except Exception as e:
+                if not return_exceptions:
+                    raise
+                out[i] = e
+        return out
