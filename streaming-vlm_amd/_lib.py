@@ -89,29 +89,50 @@ SIGNATURES = {
 }
 
 _lib = None
+_extra = {}          # explicit path -> handle (the diagnostic library next to the product one)
+
+# exported by the diagnostic build (-DSVLM_TUNING) only; bound when present, never part of include/svlm.h
+DIAG_SIGNATURES = {
+    "svlm_diag_last_gemm_plan": (_i, [_p, _i]),
+}
+DIAG_LIB_PATH = os.path.join(_HERE, "build", "libsvlm_hip_diag.so")
 
 
-def load():
-    """Load the library once; raise loudly when it is absent (no CPU / torch fallback exists)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
+def _bind(path):
+    if not os.path.exists(path):
         raise SvlmError(
-            f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
+            f"{path} not found: the HIP extension is not built. Run `python -c \"import __graft_entry__ as g; "
             f"g.build()\"` at the repo root (needs hipcc). There is no fallback path.")
-    lib = C.CDLL(LIB_PATH)
+    lib = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError = ABI mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in DIAG_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     if lib.svlm_abi_version() != 1:
-        raise SvlmError(f"libsvlm_hip.so ABI version {lib.svlm_abi_version()} != 1")
-    _lib = lib
+        raise SvlmError(f"{os.path.basename(path)} ABI version {lib.svlm_abi_version()} != 1")
     return lib
 
 
-def check(rc: int, what: str = ""):
+def load(path=None):
+    """Load the library once; raise loudly when it is absent (no CPU / torch fallback exists).  `path`: another build of the same
+    ABI (the diagnostic library), bound once per path next to the product handle."""
+    global _lib
+    if path is not None:
+        key = os.path.abspath(path)
+        if key not in _extra:
+            _extra[key] = _bind(key)
+        return _extra[key]
+    if _lib is None:
+        _lib = _bind(LIB_PATH)
+    return _lib
+
+
+def check(rc: int, what: str = "", lib=None):
     if rc != SVLM_OK:
-        msg = load().svlm_last_error()
+        msg = (lib or load()).svlm_last_error()
         raise SvlmError(f"{what} failed with status {rc}: {msg.decode() if msg else ''}")

@@ -164,6 +164,18 @@ static inline const char* svlm_env(const char* name) { return getenv(name); }
 static inline const char* svlm_env(const char*) { return nullptr; }
 #endif
 
+// Diagnostic build only: the GEMM launchers note the plan they launched (tile rows, waves, ring stages, DMA or register-staged,
+// live K-splits, K per split, whether the tuned table matched, whether the norm rode in the split-K reduce) and
+// svlm_diag_last_gemm_plan (gemm.hip) hands the note to the tests that force plans through the switches above.  SVLM_DIAG(...)
+// compiles to nothing in the product library, which has neither the note nor the export.
+#ifdef SVLM_TUNING
+struct SvlmGemmPlanNote { int seq, fp8, bm, waves, stages, dma, splits, kps, table, norm_fused; };
+extern SvlmGemmPlanNote g_svlm_gemm_plan_note;
+#define SVLM_DIAG(...) do { __VA_ARGS__; } while (0)
+#else
+#define SVLM_DIAG(...) do { } while (0)
+#endif
+
 void svlm_set_error(const char* fmt, ...);
 #define SVLM_CHECK_ARG(cond, ...)                    \
   do {                                               \

@@ -583,6 +583,19 @@ extern "C" int svlm_layernorm(const void* x, const void* w, const void* b, void*
 static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void* bias, const void* residual, int ldr,
                      void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, void* stream,
                      const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn);
+#ifdef SVLM_TUNING
+// What the last svlm_gemm_bf16* / svlm_gemm_fp8* call of this process launched (diagnostic library only, see common.h).
+// out[0..9] = {calls so far, 1 for the fp8 GEMM, tile rows, waves, ring stages, 1 = LDS-DMA / 0 = register-staged, live K-splits,
+// K per split, 1 = a tuned-table entry set the plan, 1 = the norm rode in the split-K reduce}; returns how many it wrote.
+SvlmGemmPlanNote g_svlm_gemm_plan_note = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+extern "C" int svlm_diag_last_gemm_plan(int* out, int n) {
+  const SvlmGemmPlanNote& p = g_svlm_gemm_plan_note;
+  const int v[10] = {p.seq, p.fp8, p.bm, p.waves, p.stages, p.dma, p.splits, p.kps, p.table, p.norm_fused};
+  int i = 0;
+  for (; i < n && i < 10; ++i) out[i] = v[i];
+  return i;
+}
+#endif
 int svlm_gemm_reduce_launch(const float* partial, int splits, const void* bias, const void* residual, int ldr, void* C, int ldc, int M, int N,
                             int act, const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn, void* stream, void* XN8 = nullptr,
                             int ldxn8 = 0, float* xn_scale = nullptr);
@@ -661,6 +674,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
       {4, 2048, 5120, 64, 4},      // merger mlp.2 -> 3B: 19.7 vs 21.5
   };
   bool plan_w8 = false, plan_ns2 = false;
+  bool table_hit = false;
   if (svlm_env("SVLM_GEMM_NO_TABLE") == nullptr) {
     const int mb = (M + 63) / 64;
     for (const GemmPlan& p : kTunedPlans) {
@@ -669,6 +683,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
         best_splits = p.splits;
         plan_w8 = p.variant == 1;
         plan_ns2 = p.variant == 2;
+        table_hit = true;
         break;
       }
     }
@@ -677,7 +692,9 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
   // per CU -- 610-740 -> 710-820 TFLOP/s against the 64-row tiles (tools/gemm_big.py); K = 1280 (the ViT's batches) gains nothing
   // and 256 x 128 tiles (8 waves, one workgroup per CU) where their grid fills whole rounds of the 256 CUs: 7B down_proj 821 -> 927,
   // gate/up 820 -> 886 TFLOP/s; 7B qkv (576 tiles = 2.25 rounds) stays on the 128-row tiles
-  if (M >= 2048 && K >= 2048 && best_splits == 1 && svlm_env("SVLM_GEMM_NO_T128") == nullptr) {
+  // (the 256-row tile exists on the LDS-DMA kernel only: a K that is not a multiple of 64 keeps the cost model's register-staged plan)
+  const bool dma = (K % GEMM_BK == 0) && svlm_env("SVLM_GEMM_NO_DMA") == nullptr;
+  if (dma && M >= 2048 && K >= 2048 && best_splits == 1 && svlm_env("SVLM_GEMM_NO_T128") == nullptr) {
     const long long t256 = (long long)((M + 255) / 256) * gn;
     const long long rounds = (t256 + 255) / 256;
     best_bm = (t256 * 100 >= rounds * 256 * 85) ? 256 : 128;
@@ -686,6 +703,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
     const int fb = atoi(force);
     best_bm = (fb == 192 || fb == 320 || fb == 256) ? fb : (fb == 128 && M > 64 ? 128 : 64);
     plan_w8 = plan_ns2 = false;
+    table_hit = false;
     if (const char* fs = svlm_env("SVLM_GEMM_SPLITS")) best_splits = atoi(fs) > 0 ? atoi(fs) : 1; else best_splits = 1;
     if ((long long)best_splits * M * N * 4 > ws_bytes || ws == nullptr || K < 1024) best_splits = 1;
   }
@@ -705,6 +723,8 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
   float* partial = splits > 1 ? (float*)ws : nullptr;
   const int nblocks = splits > 1 ? gn * gm * splits : 8 * ((gn + 7) / 8) * gm;
   dim3 grid(nblocks, 1, 1);
+  // waves / stages / dma are filled in where the kernel is picked below; a call that fails before its launch leaves them 0
+  SVLM_DIAG(g_svlm_gemm_plan_note = SvlmGemmPlanNote{g_svlm_gemm_plan_note.seq + 1, 0, bm, 0, 0, 0, splits, kps, table_hit ? 1 : 0, 0});
   // LDS: two stages of (BM + 128) rows x 144 B -- above the 64 KB default for TM = 4, so opt in once
   constexpr int LDS2 = 2 * (64 + GEMM_BN) * GEMM_LD * 2, LDS4 = 2 * (128 + GEMM_BN) * GEMM_LD * 2;
   static bool attr_done = false;
@@ -717,7 +737,6 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
     }
     attr_done = true;
   }
-  const bool dma = (K % GEMM_BK == 0) && svlm_env("SVLM_GEMM_NO_DMA") == nullptr;
   if (!dma && (bm == 192 || bm == 320 || bm == 256 || swiglu)) {
     svlm_set_error("svlm_gemm_bf16: tall tiles and SVLM_ACT_SWIGLU run on the LDS-DMA kernel only (K %% 64 == 0, SVLM_GEMM_NO_DMA unset)");
     return SVLM_EINVAL;
@@ -737,7 +756,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
       dma_attr_done = true;
     }
     const bool tall_unsplit_ns2 = M >= 2048 || plan_ns2 || svlm_env("SVLM_GEMM_T128NS2") != nullptr;
-    static const bool w8_128 = svlm_env("SVLM_GEMM_W8") != nullptr;       // tuning aid: force the 8-wave 128 x 128 tile
+    const bool w8_128 = svlm_env("SVLM_GEMM_W8") != nullptr;              // tuning aid: force the 8-wave 128 x 128 tile
     if (bm == 128 && splits == 1 && !swiglu && (w8_128 || plan_w8)) {
       constexpr int DL = 3 * (128 + GEMM_BN) * 128;
       static bool w8s_done = false;
@@ -745,6 +764,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<2, 3, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, DL);
         w8s_done = true;
       }
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 8; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
       gemm_glds_kernel<2, 3, 4><<<grid, 512, DL, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                   (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
     } else if (bm == 256) {
@@ -758,6 +778,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
         }
         w8_done = true;
       }
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 8; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
       gemm_glds_kernel<4, NS8, 4><<<grid, 512, DLDS8, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                     (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
     } else if (bm == 192 || bm == 320) {
@@ -774,6 +795,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
         }
         tall_attr_done = true;
       }
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = bm == 192 ? 3 : 2; g_svlm_gemm_plan_note.dma = 1);
       if (bm == 192)
         gemm_glds_kernel<6, 3><<<grid, 256, DLDS6, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                  (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
@@ -794,6 +816,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
         }
         ns2_done = true;
       }
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 1);
       gemm_glds_kernel<2, 2><<<grid, 256, DLDS2S, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
     } else if (!small && splits == 1 && tall_unsplit_ns2) {
@@ -809,19 +832,24 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
         }
         ns2t_done = true;
       }
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 1);
       gemm_glds_kernel<4, 2><<<grid, 256, DLDS4S, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
     } else if (small) {
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
       gemm_glds_kernel<2, NS2><<<grid, 256, DLDS2, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
     } else {
+      SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
       gemm_glds_kernel<4, NS4><<<grid, 256, DLDS4, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                                (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
     }
   } else if (small) {
+    SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 0);
     gemm_bf16_kernel<2><<<grid, 256, LDS2, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                              (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
   } else {
+    SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 0);
     gemm_bf16_kernel<4><<<grid, 256, LDS4, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
                                              (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
   }
@@ -837,6 +865,7 @@ int svlm_gemm_reduce_launch(const float* partial, int splits, const void* bias, 
   hipStream_t st = (hipStream_t)stream;
   int rc;
   if (splits > 1 && norm_w != nullptr && N <= 2048 * RN_IT) {      // reduce + RMSNorm of the reduced row in one launch
+    SVLM_DIAG(g_svlm_gemm_plan_note.norm_fused = 1);
     gemm_splitk_reduce_norm_kernel<<<M, 256, 0, st>>>(partial, splits, (const bf16_t*)bias, (const bf16_t*)residual, ldr, (bf16_t*)C,
                                                                 ldc, M, N, act, (const bf16_t*)norm_w, (const bf16_t*)norm_b, eps, (bf16_t*)XN, ldxn,
                                                                 norm_b ? (unsigned char*)XN8 : nullptr, ldxn8, xn_scale);

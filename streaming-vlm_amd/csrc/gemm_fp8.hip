@@ -287,6 +287,7 @@ static int gemm_fp8_impl(const void* A8, int lda, const float* a_scale, const vo
   const int gm = (M + bm - 1) / bm;
   float* partial = splits > 1 ? (float*)ws : nullptr;
   const int nblocks = splits > 1 ? gn * gm * splits : 8 * ((gn + 7) / 8) * gm;
+  SVLM_DIAG(g_svlm_gemm_plan_note = SvlmGemmPlanNote{g_svlm_gemm_plan_note.seq + 1, 1, bm, 4, 3, 1, splits, kps, 0, 0});
   constexpr int L2 = 3 * (64 + F8_BN) * 128, L4 = 3 * (128 + F8_BN) * 128;
   static bool attr_done = false;
   if (!attr_done) {

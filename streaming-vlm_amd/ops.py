@@ -6,6 +6,8 @@ calls can be captured in a HIP graph (`torch.cuda.graph`).
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 
 from . import _lib
@@ -61,8 +63,9 @@ class HipOps:
 
     name = "hip"
 
-    def __init__(self):
-        self.lib = _lib.load()
+    def __init__(self, lib_path=None):
+        self.lib = _lib.load(lib_path)      # lib_path: another build of the same ABI (tests hold the diagnostic library this way)
+        self._check = functools.partial(check, lib=self.lib)      # error text comes from the handle that made the call
         if not torch.cuda.is_available():
             raise _lib.SvlmError("no HIP device visible: the svlm hot path only runs on an MI355X (gfx950) GPU")
         self._gemm_ws = {}          # per-device fp32 scratch for split-K slabs
@@ -101,7 +104,7 @@ class HipOps:
             assert tuple(residual.shape) == (M, N)
             ldr = residual.stride(0)
         ws = self._ws(A.device)
-        check(self.lib.svlm_gemm_bf16(_ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(bias), _ptr(residual), ldr,
+        self._check(self.lib.svlm_gemm_bf16(_ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(bias), _ptr(residual), ldr,
                                       _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _stream()), "svlm_gemm_bf16")
         return out
 
@@ -122,10 +125,21 @@ class HipOps:
         if bias is not None:
             _req(bias, BF16, "gemm_norm.bias", 1)
         ws = self._ws(A.device)
-        check(self.lib.svlm_gemm_bf16_norm(_ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(bias), _ptr(residual), ldr, _ptr(out),
+        self._check(self.lib.svlm_gemm_bf16_norm(_ptr(A), A.stride(0), _ptr(W), W.stride(0), _ptr(bias), _ptr(residual), ldr, _ptr(out),
                                            out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _ptr(norm_w), _ptr(norm_b), float(eps),
                                            _ptr(out_norm), out_norm.stride(0), _stream()), "svlm_gemm_bf16_norm")
         return out, out_norm
+
+    def last_gemm_plan(self):
+        """What the last gemm / gemm_norm / gemm_fp8 call of this process launched; diagnostic library only."""
+        fn = getattr(self.lib, "svlm_diag_last_gemm_plan", None)
+        if fn is None:
+            raise _lib.SvlmError("last_gemm_plan: the product library keeps no plan note; bind HipOps to the diagnostic library")
+        import ctypes
+        v = (ctypes.c_int * 10)()
+        n = fn(v, 10)
+        keys = ("seq", "fp8", "bm", "waves", "stages", "dma", "splits", "kps", "table", "norm_fused")
+        return dict(zip(keys[:n], list(v)[:n]))
 
     # ------------------------------------------------------------------ fp8 (BASELINE configs[4]: ViT GEMMs on the fp8 MFMA path)
     FP8 = torch.float8_e4m3fn
@@ -140,7 +154,7 @@ class HipOps:
             scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
         _req(q, self.FP8, "quant_fp8.q", 2); _req(scale, torch.float32, "quant_fp8.scale", 1)
         assert tuple(q.shape) == (rows, cols) and scale.numel() == rows
-        check(self.lib.svlm_quant_rows_fp8(_ptr(x), x.stride(0), _ptr(q), q.stride(0), _ptr(scale), rows, cols, _stream()), "svlm_quant_rows_fp8")
+        self._check(self.lib.svlm_quant_rows_fp8(_ptr(x), x.stride(0), _ptr(q), q.stride(0), _ptr(scale), rows, cols, _stream()), "svlm_quant_rows_fp8")
         return q, scale
 
     def gemm_fp8(self, A8, a_scale, W8, w_scale, bias=None, residual=None, out=None, act=ACT_NONE, norm_w=None, norm_b=None, eps=1e-6,
@@ -173,11 +187,11 @@ class HipOps:
             q8, qs = out_norm_q
             _req(q8, self.FP8, "gemm_fp8.out_norm_q", 2); _req(qs, torch.float32, "gemm_fp8.out_norm_scale", 1)
             assert norm_w is not None and tuple(q8.shape) == (M, N) and qs.numel() == M
-            check(self.lib.svlm_gemm_fp8_normq(_ptr(A8), A8.stride(0), _ptr(a_scale), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual),
+            self._check(self.lib.svlm_gemm_fp8_normq(_ptr(A8), A8.stride(0), _ptr(a_scale), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual),
                                                ldr, _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _ptr(norm_w), _ptr(norm_b),
                                                float(eps), _ptr(out_norm), ldxn, _ptr(q8), q8.stride(0), _ptr(qs), _stream()), "svlm_gemm_fp8_normq")
             return out
-        check(self.lib.svlm_gemm_fp8(_ptr(A8), A8.stride(0), _ptr(a_scale), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), ldr,
+        self._check(self.lib.svlm_gemm_fp8(_ptr(A8), A8.stride(0), _ptr(a_scale), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), ldr,
                                      _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _ptr(norm_w), _ptr(norm_b), float(eps),
                                      _ptr(out_norm), ldxn, _stream()), "svlm_gemm_fp8")
         return out
@@ -197,14 +211,14 @@ class HipOps:
             _req(bias, BF16, "gemv.bias"); assert bias.numel() == N
         if residual is not None:
             _req(residual, BF16, "gemv.residual"); assert residual.numel() == N
-        check(self.lib.svlm_gemv_bf16(_ptr(x), _ptr(W), W.stride(0), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_f32),
+        self._check(self.lib.svlm_gemv_bf16(_ptr(x), _ptr(W), W.stride(0), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_f32),
                                       N, K, act, _stream()), "svlm_gemv_bf16")
         return out if out is not None else out_f32
 
     def prefetch(self, t, n_wgs=256):
         """Infinity-Cache warm-up of a contiguous tensor on the CURRENT stream (callers put it on a side stream)."""
         assert t.is_cuda and t.is_contiguous()
-        check(self.lib.svlm_prefetch(_ptr(t), t.numel() * t.element_size(), int(n_wgs), _stream()), "svlm_prefetch")
+        self._check(self.lib.svlm_prefetch(_ptr(t), t.numel() * t.element_size(), int(n_wgs), _stream()), "svlm_prefetch")
 
     def rmsnorm(self, x, w, eps, out=None):
         _req(x, BF16, "rmsnorm.x"); _req(w, BF16, "rmsnorm.w", 1)
@@ -214,7 +228,7 @@ class HipOps:
         if out is None:
             out = torch.empty_like(x)
         _req(out, BF16, "rmsnorm.out"); assert out.is_contiguous() and out.numel() == x.numel()
-        check(self.lib.svlm_rmsnorm(_ptr(x), _ptr(w), _ptr(out), rows, cols, float(eps), _stream()), "svlm_rmsnorm")
+        self._check(self.lib.svlm_rmsnorm(_ptr(x), _ptr(w), _ptr(out), rows, cols, float(eps), _stream()), "svlm_rmsnorm")
         return out
 
     def layernorm(self, x, w, b, eps, out=None):
@@ -225,7 +239,7 @@ class HipOps:
         if out is None:
             out = torch.empty_like(x)
         _req(out, BF16, "layernorm.out"); assert out.is_contiguous() and out.numel() == x.numel()
-        check(self.lib.svlm_layernorm(_ptr(x), _ptr(w), _ptr(b), _ptr(out), rows, cols, float(eps), _stream()), "svlm_layernorm")
+        self._check(self.lib.svlm_layernorm(_ptr(x), _ptr(w), _ptr(b), _ptr(out), rows, cols, float(eps), _stream()), "svlm_layernorm")
         return out
 
     def add(self, a, b, out=None):
@@ -233,7 +247,7 @@ class HipOps:
         assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
         if out is None:
             out = torch.empty_like(a)
-        check(self.lib.svlm_add(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "svlm_add")
+        self._check(self.lib.svlm_add(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "svlm_add")
         return out
 
     def silu_mul(self, gu, out=None):
@@ -243,7 +257,7 @@ class HipOps:
         if out is None:
             out = torch.empty((rows, two_i // 2), dtype=BF16, device=gu.device)
         assert out.is_contiguous() and tuple(out.shape) == (rows, two_i // 2)
-        check(self.lib.svlm_silu_mul(_ptr(gu), _ptr(out), rows, two_i // 2, _stream()), "svlm_silu_mul")
+        self._check(self.lib.svlm_silu_mul(_ptr(gu), _ptr(out), rows, two_i // 2, _stream()), "svlm_silu_mul")
         return out
 
     def gather_rows(self, table, alt, idx, out, idx_off=None):
@@ -256,7 +270,7 @@ class HipOps:
             assert idx.numel() >= rows
         else:
             _req(idx_off, torch.int32, "gather.idx_off")
-        check(self.lib.svlm_gather_rows(_ptr(table), _ptr(alt), _ptr(idx), _ptr(idx_off), _ptr(out), rows, cols, _stream()),
+        self._check(self.lib.svlm_gather_rows(_ptr(table), _ptr(alt), _ptr(idx), _ptr(idx_off), _ptr(out), rows, cols, _stream()),
               "svlm_gather_rows")
         return out
 
@@ -273,7 +287,7 @@ class HipOps:
         _req(out, BF16, "patchify.out", 2)
         assert out.is_contiguous() and tuple(out.shape) == (gt * gh * gw, cols)
         f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))          # the exact fp32 constants torch.tensor(list) holds
-        check(self.lib.svlm_patchify_u8(_ptr(frames), _ptr(out), T, H, W, patch, temporal, merge, f32(mean[0]), f32(mean[1]), f32(mean[2]),
+        self._check(self.lib.svlm_patchify_u8(_ptr(frames), _ptr(out), T, H, W, patch, temporal, merge, f32(mean[0]), f32(mean[1]), f32(mean[2]),
                                         f32(std[0]), f32(std[1]), f32(std[2]), _stream()), "svlm_patchify_u8")
         return out, [[gt, gh, gw]]
 
@@ -303,7 +317,7 @@ class HipOps:
         if ws is None or ws.numel() * 4 < need:
             ws = torch.empty(max(need // 4, 1 << 18), dtype=torch.float32, device=frames.device)
             self._gemm_ws["rz" + str(frames.device)] = ws
-        check(self.lib.svlm_resize_bicubic_aa_u8(_ptr(frames), _ptr(out), T * Cc, H, W, h, w, _ptr(xmin), _ptr(xsize), _ptr(wx),
+        self._check(self.lib.svlm_resize_bicubic_aa_u8(_ptr(frames), _ptr(out), T * Cc, H, W, h, w, _ptr(xmin), _ptr(xsize), _ptr(wx),
                                                  wx.shape[1], _ptr(ymin), _ptr(ysize), _ptr(wy), wy.shape[1], _ptr(ws),
                                                  ws.numel() * 4, _stream()), "svlm_resize_bicubic_aa_u8")
         return out
@@ -314,7 +328,7 @@ class HipOps:
         N = qkv.shape[0]
         assert qkv.is_contiguous() and qkv.shape[1] == 3 * H * d
         assert cosT.is_contiguous() and sinT.is_contiguous() and tuple(cosT.shape) == (N, d // 2) == tuple(sinT.shape)
-        check(self.lib.svlm_vit_rope(_ptr(qkv), _ptr(cosT), _ptr(sinT), N, H, d, _stream()), "svlm_vit_rope")
+        self._check(self.lib.svlm_vit_rope(_ptr(qkv), _ptr(cosT), _ptr(sinT), N, H, d, _stream()), "svlm_vit_rope")
         return qkv
 
     def vit_attn(self, qkv, n_seq, seq_len, H, d, scale, out=None):
@@ -324,7 +338,7 @@ class HipOps:
         if out is None:
             out = torch.empty((N, H * d), dtype=BF16, device=qkv.device)
         assert out.is_contiguous() and tuple(out.shape) == (N, H * d)
-        check(self.lib.svlm_vit_attn(_ptr(qkv), _ptr(out), n_seq, seq_len, H, d, float(scale), _stream()), "svlm_vit_attn")
+        self._check(self.lib.svlm_vit_attn(_ptr(qkv), _ptr(out), n_seq, seq_len, H, d, float(scale), _stream()), "svlm_vit_attn")
         return out
 
     # ------------------------------------------------------------------ rope table / KV pool
@@ -337,7 +351,7 @@ class HipOps:
         assert 0 <= start and start + count <= min(pos3.shape[1], rope_cs.shape[0]), (start, count, pos3.shape, rope_cs.shape)
         is_f = pos3.dtype == torch.float32
         assert is_f or pos3.dtype == torch.int32
-        check(self.lib.svlm_mrope_table(0 if is_f else _ptr(pos3), _ptr(pos3) if is_f else 0, pos3.shape[1], _ptr(inv_freq),
+        self._check(self.lib.svlm_mrope_table(0 if is_f else _ptr(pos3), _ptr(pos3) if is_f else 0, pos3.shape[1], _ptr(inv_freq),
                                         _ptr(rope_cs), start, count, D, sections[0], sections[1], sections[2], _stream()),
               "svlm_mrope_table")
 
@@ -353,7 +367,7 @@ class HipOps:
         is_f = pos3.dtype == torch.float32
         assert is_f or pos3.dtype == torch.int32
         assert ws.numel() * 4 >= self.lib.svlm_rope_index_ws_bytes(max(int(L), 1), int(n_grids))
-        check(self.lib.svlm_rope_index(_ptr(ids), int(L), _ptr(grids), int(n_grids), int(merge), int(video_token_id), int(vision_start_token_id),
+        self._check(self.lib.svlm_rope_index(_ptr(ids), int(L), _ptr(grids), int(n_grids), int(merge), int(video_token_id), int(vision_start_token_id),
                                        0 if is_f else _ptr(pos3), _ptr(pos3) if is_f else 0, pos3.shape[1], float(second_per_grid_t),
                                        float(tokens_per_second), int(n_extra), _ptr(ws), ws.numel() * 4, _stream()), "svlm_rope_index")
 
@@ -372,7 +386,7 @@ class HipOps:
         toks = (ctypes.c_int * 11)(TOKEN_IDS["<|im_start|>"], TOKEN_IDS["<|im_end|>"], TOKEN_IDS["user"], TOKEN_IDS["assistant"],
                                    TOKEN_IDS["<|vision_start|>"], TOKEN_IDS["<|vision_end|>"], TOKEN_IDS["<|video_pad|>"], TOKEN_IDS["\n"],
                                    pt[0], pt[1], TOKEN_IDS["Time"])
-        check(self.lib.svlm_evict_plan(_ptr(d_ids), L, {"sink_window": 0, "structural": 1}[policy], int(round_i), int(text_round), int(visual_round),
+        self._check(self.lib.svlm_evict_plan(_ptr(d_ids), L, {"sink_window": 0, "structural": 1}[policy], int(round_i), int(text_round), int(visual_round),
                                        -1 if text_sink is None else int(text_sink), -1 if text_sliding_window is None else int(text_sliding_window),
                                        int(assistant_start_bias), int(assistant_end_bias), int(sink), int(window), int(kv_len),
                                        ctypes.cast(toks, ctypes.c_void_p), _ptr(ws), ws.numel() * 4, _stream()), "svlm_evict_plan")
@@ -401,7 +415,7 @@ class HipOps:
         if len_dev is None:
             assert 0 <= start and start + T <= slot_of.numel(), (start, T, slot_of.numel())
         kp, vp = self._planes(pool, layer)
-        check(self.lib.svlm_kv_append(_ptr(k_new), k_new.stride(0), _ptr(v_new), v_new.stride(0), _ptr(kp), _ptr(vp), _ptr(slot_of),
+        self._check(self.lib.svlm_kv_append(_ptr(k_new), k_new.stride(0), _ptr(v_new), v_new.stride(0), _ptr(kp), _ptr(vp), _ptr(slot_of),
                                       _ptr(len_dev), start, T, Hkv, D, n_slots, _stream()), "svlm_kv_append")
 
     def kv_move_rows(self, pool, src, dst):
@@ -409,14 +423,14 @@ class HipOps:
         Ly, two, Hkv, n_slots, D = pool.shape
         n = src.numel()
         assert pool.is_contiguous() and dst.numel() == n
-        check(self.lib.svlm_kv_move_rows(_ptr(pool), Ly * two * Hkv, n_slots, D, _ptr(src), _ptr(dst), n, _stream()), "svlm_kv_move_rows")
+        self._check(self.lib.svlm_kv_move_rows(_ptr(pool), Ly * two * Hkv, n_slots, D, _ptr(src), _ptr(dst), n, _stream()), "svlm_kv_move_rows")
 
     def kv_gather(self, pool, layer, which, slot_of, L):
         _req(pool, BF16, "kv_gather.pool", 5); _req(slot_of, torch.int32, "kv_gather.slot_of", 1)
         _, _, Hkv, n_slots, D = pool.shape
         assert slot_of.numel() >= L
         out = torch.empty((Hkv, L, D), dtype=BF16, device=pool.device)
-        check(self.lib.svlm_kv_gather(_ptr(pool[layer, which]), _ptr(slot_of), _ptr(out), L, Hkv, D, n_slots, _stream()), "svlm_kv_gather")
+        self._check(self.lib.svlm_kv_gather(_ptr(pool[layer, which]), _ptr(slot_of), _ptr(out), L, Hkv, D, n_slots, _stream()), "svlm_kv_gather")
         return out
 
     # ------------------------------------------------------------------ attention
@@ -453,7 +467,7 @@ class HipOps:
             assert 0 < length <= max_len, (length, max_len)
         kp, vp = self._planes(pool, layer)
         kl, vl, lin_rows, lin_len = self._lin_args(lin, layer, Hkv, D, max_len, "decode_attn")
-        check(self.lib.svlm_decode_attn_lin(_ptr(q), _ptr(kp), _ptr(vp), _ptr(slot_of), _ptr(rope_cs), _ptr(len_dev), length,
+        self._check(self.lib.svlm_decode_attn_lin(_ptr(q), _ptr(kp), _ptr(vp), _ptr(slot_of), _ptr(rope_cs), _ptr(len_dev), length,
                                             _ptr(kl), _ptr(vl), lin_rows, _ptr(lin_len), _ptr(out), _ptr(ws), Hq, Hkv, D, n_slots, max_len,
                                             chunk, float(scale), _stream()), "svlm_decode_attn_lin")
         return out
@@ -481,7 +495,7 @@ class HipOps:
             assert k_new.stride(0) == v_new.stride(0)
             kv_stride = k_new.stride(0)
         kl, vl, lin_rows, lin_len = self._lin_args(lin, layer, Hkv, D, L, "prefill_attn")
-        check(self.lib.svlm_prefill_attn_ropeload_lin(_ptr(q), q.stride(0), _ptr(k_new), _ptr(v_new), kv_stride, _ptr(kp), _ptr(vp),
+        self._check(self.lib.svlm_prefill_attn_ropeload_lin(_ptr(q), q.stride(0), _ptr(k_new), _ptr(v_new), kv_stride, _ptr(kp), _ptr(vp),
                                                       _ptr(slot_of), _ptr(rope_cs), _ptr(out), out.stride(0), T, L, Hq, Hkv, D, n_slots,
                                                       float(scale), _ptr(ws), ws.numel() * 2, _ptr(kl), _ptr(vl), lin_rows, _ptr(lin_len),
                                                       _stream()), "svlm_prefill_attn_ropeload_lin")
@@ -491,7 +505,7 @@ class HipOps:
     def mark_seen(self, ids, n, seen):
         _req(ids, torch.int32, "mark_seen.ids", 1); _req(seen, torch.uint8, "mark_seen.seen", 1)
         assert ids.numel() >= n
-        check(self.lib.svlm_mark_seen(_ptr(ids), n, _ptr(seen), seen.numel(), _stream()), "svlm_mark_seen")
+        self._check(self.lib.svlm_mark_seen(_ptr(ids), n, _ptr(seen), seen.numel(), _stream()), "svlm_mark_seen")
 
     def sampling_ws(self, V, device):
         n = max(self.lib.svlm_argmax_ws_bytes(), self.lib.svlm_dec_lm_head_ws_bytes(V))
@@ -509,7 +523,7 @@ class HipOps:
         assert state.numel() >= 2
         _req(ws, torch.float32, "argmax.ws", 1)
         assert ws.numel() * 4 >= self.lib.svlm_argmax_ws_bytes()
-        check(self.lib.svlm_penalty_argmax(_ptr(logits), logits.numel(), _ptr(seen), float(penalty), _ptr(suppress), n_sup,
+        self._check(self.lib.svlm_penalty_argmax(_ptr(logits), logits.numel(), _ptr(seen), float(penalty), _ptr(suppress), n_sup,
                                            _ptr(tok_buf), _ptr(state), int(advance_kv), _ptr(ws), _stream()), "svlm_penalty_argmax")
 
     def penalty_sample(self, logits, seen, penalty, suppress, temperature, top_k, top_p, rng, tok_buf, state, advance_kv, ws):
@@ -524,7 +538,7 @@ class HipOps:
             _req(suppress, torch.int32, "sample.suppress", 1)
             n_sup = suppress.numel()
         assert state.numel() >= 2 and rng.numel() >= 2 and ws.numel() * 4 >= self.lib.svlm_argmax_ws_bytes()
-        check(self.lib.svlm_penalty_sample(_ptr(logits), logits.numel(), _ptr(seen), float(penalty), _ptr(suppress), n_sup, float(temperature),
+        self._check(self.lib.svlm_penalty_sample(_ptr(logits), logits.numel(), _ptr(seen), float(penalty), _ptr(suppress), n_sup, float(temperature),
                                            int(top_k), float(top_p), _ptr(rng), _ptr(tok_buf), _ptr(state), int(advance_kv), _ptr(ws),
                                            _stream()), "svlm_penalty_sample")
 
@@ -541,7 +555,7 @@ class HipOps:
             assert 0 <= length < slot_of.numel()
         kp, vp = self._planes(pool, layer)
         kl, vl, lin_rows, _ = self._lin_args(lin, layer, Hkv, D, length + 1 if len_dev is None else 1, "dec_qkv")
-        check(self.lib.svlm_dec_qkv_lin(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(bias), _ptr(q_out), _ptr(kp), _ptr(vp),
+        self._check(self.lib.svlm_dec_qkv_lin(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(bias), _ptr(q_out), _ptr(kp), _ptr(vp),
                                         _ptr(slot_of), _ptr(len_dev), int(length), K, qd, kd, D, n_slots, _ptr(kl), _ptr(vl), lin_rows,
                                         _stream()), "svlm_dec_qkv_lin")
 
@@ -549,7 +563,7 @@ class HipOps:
         _req(x, BF16, "dec_gate_up.x", 1); _req(ln_w, BF16, "dec_gate_up.ln_w", 1); _req(W, BF16, "dec_gate_up.W", 2); _req(h, BF16, "dec_gate_up.h", 1)
         N, K = W.shape
         assert N % 2 == 0 and h.numel() == N // 2 and x.numel() == K == ln_w.numel()
-        check(self.lib.svlm_dec_gate_up(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(h), N // 2, K, _stream()), "svlm_dec_gate_up")
+        self._check(self.lib.svlm_dec_gate_up(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(h), N // 2, K, _stream()), "svlm_dec_gate_up")
 
     # ---- persistent decode-layer tail (csrc/dec_tail.hip)
     def dec_tail_supported(self, H, I, qd, kd, grid=0):
@@ -568,7 +582,7 @@ class HipOps:
     def dec_tail_reset(self, ws, H, I, n_layers):
         _req(ws, torch.int64, "dec_tail_reset.ws", 1)
         assert ws.numel() * 8 >= self.lib.svlm_dec_tail_ws_bytes(int(H), int(I), int(n_layers))
-        check(self.lib.svlm_dec_tail_reset(_ptr(ws), int(H), int(I), int(n_layers), _stream()), "svlm_dec_tail_reset")
+        self._check(self.lib.svlm_dec_tail_reset(_ptr(ws), int(H), int(I), int(n_layers), _stream()), "svlm_dec_tail_reset")
 
     def dec_tail(self, attn, x, o_w, ln2, gu_w, down_w, eps, ws, layer, n_layers, nxt=None, grid=0, stamps=None):
         """One layer's tail.  `nxt` = (ln1, qkv_w, qkv_b, q_out, pool, layer_index, slot_of, qd, kd, length, len_dev) of the NEXT layer's
@@ -593,7 +607,7 @@ class HipOps:
             kp, vp = self._planes(pool, li)
             args = (_ptr(ln1), _ptr(qkv_w), qkv_w.stride(0), _ptr(qkv_b), _ptr(q_out), _ptr(kp), _ptr(vp), _ptr(slot_of), _ptr(len_dev),
                     int(length), H, I, qd, kd, D, n_slots)
-        check(self.lib.svlm_dec_tail(_ptr(attn), _ptr(x), _ptr(o_w), o_w.stride(0), _ptr(ln2), _ptr(gu_w), gu_w.stride(0), _ptr(down_w),
+        self._check(self.lib.svlm_dec_tail(_ptr(attn), _ptr(x), _ptr(o_w), o_w.stride(0), _ptr(ln2), _ptr(gu_w), gu_w.stride(0), _ptr(down_w),
                                      down_w.stride(0), *args, float(eps), _ptr(ws), int(layer), int(n_layers), int(grid), _ptr(stamps), _stream()),
               "svlm_dec_tail")
 
@@ -619,17 +633,17 @@ class HipOps:
             n_sup = suppress.numel()
         if rng is not None:
             _req(rng, torch.int32, "dec_lm_head.rng", 1); _req(state, torch.int32, "dec_lm_head.state", 1)
-            check(self.lib.svlm_dec_lm_head_sample(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), _ptr(seen), float(penalty),
+            self._check(self.lib.svlm_dec_lm_head_sample(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), _ptr(seen), float(penalty),
                                                    _ptr(suppress), n_sup, _ptr(ws), V, K, float(temperature), _ptr(rng), _ptr(state), _stream()),
                   "svlm_dec_lm_head_sample")
             return
-        check(self.lib.svlm_dec_lm_head(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), _ptr(seen), float(penalty),
+        self._check(self.lib.svlm_dec_lm_head(_ptr(x), _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), _ptr(seen), float(penalty),
                                         _ptr(suppress), n_sup, _ptr(ws), V, K, _stream()), "svlm_dec_lm_head")
 
     def argmax_finish(self, ws, V, seen, tok_buf, state, advance_kv):
         _req(ws, torch.float32, "argmax_finish.ws", 1); _req(tok_buf, torch.int32, "argmax_finish.tok_buf", 1)
         _req(state, torch.int32, "argmax_finish.state", 1)
-        check(self.lib.svlm_argmax_finish(_ptr(ws), V, _ptr(seen), _ptr(tok_buf), _ptr(state), int(advance_kv), _stream()), "svlm_argmax_finish")
+        self._check(self.lib.svlm_argmax_finish(_ptr(ws), V, _ptr(seen), _ptr(tok_buf), _ptr(state), int(advance_kv), _stream()), "svlm_argmax_finish")
 
     # ------------------------------------------------------------------ lane-batched decode step (csrc/decode_batch.hip)
     LANE_WORDS = 9          # int64 words of one svlm_lane record (include/svlm.h)
@@ -674,14 +688,14 @@ class HipOps:
         self._lanes(lanes, B, "decb_embed"); _req(table, BF16, "decb_embed.table", 2)
         assert table.is_contiguous()
         ldx = self._rows(x, B, table.shape[1], "decb_embed.x")
-        check(self.lib.svlm_decb_embed(_ptr(lanes), B, _ptr(table), table.shape[0], _ptr(x), ldx, table.shape[1], _stream()), "svlm_decb_embed")
+        self._check(self.lib.svlm_decb_embed(_ptr(lanes), B, _ptr(table), table.shape[0], _ptr(x), ldx, table.shape[1], _stream()), "svlm_decb_embed")
 
     def decb_qkv(self, lanes, B, x, ln_w, eps, W, bias, q_out, layer, qd, kd, D, n_layers):
         self._lanes(lanes, B, "decb_qkv"); _req(ln_w, BF16, "decb_qkv.ln_w", 1); _req(W, BF16, "decb_qkv.W", 2); _req(bias, BF16, "decb_qkv.bias", 1)
         N, K = W.shape
         assert N == qd + 2 * kd == bias.numel() and ln_w.numel() == K and 0 <= layer < n_layers
         ldx, ldq = self._rows(x, B, K, "decb_qkv.x"), self._rows(q_out, B, qd, "decb_qkv.q_out")
-        check(self.lib.svlm_decb_qkv(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(bias), _ptr(q_out), ldq,
+        self._check(self.lib.svlm_decb_qkv(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(bias), _ptr(q_out), ldq,
                                      int(layer), K, qd, kd, D, _stream()), "svlm_decb_qkv")
 
     def decb_gate_up(self, lanes, B, x, ln_w, eps, W, h):
@@ -689,14 +703,14 @@ class HipOps:
         N, K = W.shape
         assert N % 2 == 0 and ln_w.numel() == K
         ldx, ldh = self._rows(x, B, K, "decb_gate_up.x"), self._rows(h, B, N // 2, "decb_gate_up.h")
-        check(self.lib.svlm_decb_gate_up(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(h), ldh, N // 2, K,
+        self._check(self.lib.svlm_decb_gate_up(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(h), ldh, N // 2, K,
                                          _stream()), "svlm_decb_gate_up")
 
     def decb_gemv(self, lanes, B, x, W, residual, out):
         self._lanes(lanes, B, "decb_gemv"); _req(W, BF16, "decb_gemv.W", 2)
         N, K = W.shape
         ldx, ldr, ldy = self._rows(x, B, K, "decb_gemv.x"), self._rows(residual, B, N, "decb_gemv.residual"), self._rows(out, B, N, "decb_gemv.out")
-        check(self.lib.svlm_decb_gemv(_ptr(lanes), B, _ptr(x), ldx, _ptr(W), W.stride(0), _ptr(residual), ldr, _ptr(out), ldy, N, K, _stream()),
+        self._check(self.lib.svlm_decb_gemv(_ptr(lanes), B, _ptr(x), ldx, _ptr(W), W.stride(0), _ptr(residual), ldr, _ptr(out), ldy, N, K, _stream()),
               "svlm_decb_gemv")
 
     def decb_sampling_ws(self, V, B, device):
@@ -711,13 +725,13 @@ class HipOps:
         assert ln_w.numel() == K and suppress.numel() >= 8 and ws.is_contiguous()
         assert ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
         ldx, ldl = self._rows(x, B, K, "decb_lm_head.x"), self._rows(logits, B, V, "decb_lm_head.logits", torch.float32)
-        check(self.lib.svlm_decb_lm_head(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), ldl,
+        self._check(self.lib.svlm_decb_lm_head(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), ldl,
                                          _ptr(suppress), _ptr(ws), V, K, _stream()), "svlm_decb_lm_head")
 
     def decb_argmax_finish(self, lanes, B, ws, V, advance_kv):
         self._lanes(lanes, B, "decb_argmax_finish"); _req(ws, torch.float32, "decb_argmax_finish.ws", 2)
         assert ws.is_contiguous() and ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
-        check(self.lib.svlm_decb_argmax_finish(_ptr(lanes), B, _ptr(ws), V, int(advance_kv), _stream()), "svlm_decb_argmax_finish")
+        self._check(self.lib.svlm_decb_argmax_finish(_ptr(lanes), B, _ptr(ws), V, int(advance_kv), _stream()), "svlm_decb_argmax_finish")
 
     # ------------------------------------------------------------------ fp8 language-model weights (csrc/decode_fp8.hip)
     @staticmethod
@@ -740,7 +754,7 @@ class HipOps:
             assert 0 <= length < slot_of.numel()
         kp, vp = self._planes(pool, layer)
         kl, vl, lin_rows, _ = self._lin_args(lin, layer, Hkv, D, length + 1 if len_dev is None else 1, "dec_qkv_fp8")
-        check(self.lib.svlm_dec_qkv_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(q_out), _ptr(kp),
+        self._check(self.lib.svlm_dec_qkv_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(q_out), _ptr(kp),
                                         _ptr(vp), _ptr(slot_of), _ptr(len_dev), int(length), K, qd, kd, D, n_slots, _ptr(kl), _ptr(vl), lin_rows,
                                         _stream()), "svlm_dec_qkv_fp8")
 
@@ -748,7 +762,7 @@ class HipOps:
         _req(x, BF16, "dec_gate_up_fp8.x", 1); _req(ln_w, BF16, "dec_gate_up_fp8.ln_w", 1); _req(h, BF16, "dec_gate_up_fp8.h", 1)
         N, K = self._req_fp8(W8, w_scale, "dec_gate_up_fp8")
         assert N % 2 == 0 and h.numel() == N // 2 and x.numel() == K == ln_w.numel()
-        check(self.lib.svlm_dec_gate_up_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(h), N // 2, K, _stream()),
+        self._check(self.lib.svlm_dec_gate_up_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(h), N // 2, K, _stream()),
               "svlm_dec_gate_up_fp8")
 
     def gemv_fp8(self, x, W8, w_scale, bias=None, residual=None, out=None, out_f32=None):
@@ -766,7 +780,7 @@ class HipOps:
             _req(bias, BF16, "gemv_fp8.bias"); assert bias.numel() == N
         if residual is not None:
             _req(residual, BF16, "gemv_fp8.residual"); assert residual.numel() == N
-        check(self.lib.svlm_gemv_fp8(_ptr(x), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_f32),
+        self._check(self.lib.svlm_gemv_fp8(_ptr(x), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_f32),
                                      N, K, ACT_NONE, _stream()), "svlm_gemv_fp8")
         return out if out is not None else out_f32
 
@@ -785,11 +799,11 @@ class HipOps:
             n_sup = suppress.numel()
         if rng is not None:
             _req(rng, torch.int32, "dec_lm_head_fp8.rng", 1); _req(state, torch.int32, "dec_lm_head_fp8.state", 1)
-            check(self.lib.svlm_dec_lm_head_sample_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(logits),
+            self._check(self.lib.svlm_dec_lm_head_sample_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(logits),
                                                        _ptr(seen), float(penalty), _ptr(suppress), n_sup, _ptr(ws), V, K, float(temperature),
                                                        _ptr(rng), _ptr(state), _stream()), "svlm_dec_lm_head_sample_fp8")
             return
-        check(self.lib.svlm_dec_lm_head_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(logits), _ptr(seen),
+        self._check(self.lib.svlm_dec_lm_head_fp8(_ptr(x), _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(logits), _ptr(seen),
                                             float(penalty), _ptr(suppress), n_sup, _ptr(ws), V, K, _stream()), "svlm_dec_lm_head_fp8")
 
     def dequant_fp8(self, W8, w_scale, out):
@@ -798,5 +812,5 @@ class HipOps:
         _req(out, BF16, "dequant_fp8.out", 2)
         if tuple(out.shape) != (N, K) or not W8.is_contiguous() or not out.is_contiguous():
             raise _lib.SvlmError(f"dequant_fp8: out {tuple(out.shape)} vs W8 {tuple(W8.shape)}, both contiguous")
-        check(self.lib.svlm_dequant_fp8_bf16(_ptr(W8), _ptr(w_scale), _ptr(out), N, K, _stream()), "svlm_dequant_fp8_bf16")
+        self._check(self.lib.svlm_dequant_fp8_bf16(_ptr(W8), _ptr(w_scale), _ptr(out), N, K, _stream()), "svlm_dequant_fp8_bf16")
         return out

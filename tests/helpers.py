@@ -1,6 +1,9 @@
 """Shared test helpers: config bridging between the product and the oracle, chunk sources."""
 from __future__ import annotations
 
+import contextlib
+import os
+
 import torch
 
 from oracle import generate as og
@@ -88,3 +91,29 @@ def run_engine_stream(model, n_chunks, size=56, fps=1.0, policy="sink_window", s
                                 window=window, do_sample=False, max_new_tokens=max_new, suppress_eos=suppress_eos, quiet=True,
                                 trace=trace, token_counts=counts, ids_log=ids_log, **kw)
     return res, trace, counts, ids_log
+
+
+# ------------------------------------------------------------------------------------------------ the diagnostic library
+def diag_ops():
+    """HipOps bound to the diagnostic library (-DSVLM_TUNING: reads the SVLM_* tuning switches, reports the plan of the last GEMM).
+    The product library reads no environment, so a test that forces a plan MUST go through this and `forced_switches`.  A missing
+    library is an error, not a skip."""
+    from streaming_vlm_amd import _lib
+    from streaming_vlm_amd.ops import HipOps
+    assert os.path.exists(_lib.DIAG_LIB_PATH), (f"{_lib.DIAG_LIB_PATH} is missing: build it with "
+                                                "`python -c \"import __graft_entry__ as g; g.build()\"` at the repository root")
+    return HipOps(lib_path=_lib.DIAG_LIB_PATH)
+
+
+@contextlib.contextmanager
+def forced_switches(env):
+    """Set tuning switches (a dict, e.g. {"SVLM_GEMM_BM": "192"}) for the diagnostic library for the duration of the block; every
+    SVLM_GEMM* switch already in the environment is taken out first and put back afterwards."""
+    saved = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith("SVLM_GEMM")}
+    try:
+        os.environ.update({k: str(v) for k, v in (env or {}).items()})
+        yield
+    finally:
+        for k in (env or {}):
+            os.environ.pop(k, None)
+        os.environ.update(saved)

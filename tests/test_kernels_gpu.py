@@ -22,6 +22,12 @@ def ops():
 
 
 @pytest.fixture(scope="module")
+def diag():
+    import helpers as H
+    return H.diag_ops()
+
+
+@pytest.fixture(scope="module")
 def ref():
     from ref_ops import RefOps
     return RefOps()
@@ -62,7 +68,8 @@ def close(name, got, want, max_tol=2 ** -7, mean_tol=1e-3):
     (275, 1536, 1536, False, True, 0),      # 2B o_proj + residual (split-K)
     (1024, 1280, 1280, True, True, 0),      # ViT proj (split-K 2)
     (64, 256, 4096, True, False, 1),        # deep split-K with activation
-    (200, 128, 1000, False, False, 0),      # K not a multiple of 64, split-K tail
+    (200, 128, 1000, False, False, 0),      # K not a multiple of 64 (register-staged kernel); K < 1024, so no split-K
+    (70, 132, 1176, False, False, 0),       # K not a multiple of 64 AND split-K with a K tail (2 splits of 640)
     # shapes that take their (tile rows, split-K) from the tuned-plan table rather than from the cost model
     (290, 3584, 18944, False, True, 0),     # 7B down_proj (BM 128, 3 splits)
     (290, 4608, 3584, True, False, 0),      # 7B qkv (BM 64, 2 splits)
@@ -86,15 +93,22 @@ def test_gemm(ops, ref, M, N, K, bias, res, act):
 
 
 @pytest.mark.parametrize("bm,splits", [(64, 1), (64, 5), (128, 1), (128, 3), (128, 8), (192, 1), (192, 4), (320, 1), (320, 8), (256, 1), (256, 4)])
-def test_gemm_every_plan_is_numerically_the_same_op(ops, ref, bm, splits, monkeypatch):
-    """Tile height and split-K are performance choices only: forced through the tuning switches, each plan must pass the
-    same bar as the default one."""
-    monkeypatch.setenv("SVLM_GEMM_BM", str(bm))
-    monkeypatch.setenv("SVLM_GEMM_SPLITS", str(splits))
+def test_gemm_every_plan_is_numerically_the_same_op(diag, ref, bm, splits):
+    """Tile height and split-K are performance choices only: forced through the tuning switches ON THE DIAGNOSTIC LIBRARY (the
+    product library reads no environment), each plan must pass the same bar as the default one, and the library must report that it
+    launched the forced plan.  tests/test_gemm_paths_gpu.py holds every plan to an fp64 per-element bound at ragged shapes."""
+    import helpers as H
+    import gemm_paths as G
     M, N, K = 290, 1536, 8960
     A, W, b, r_ = rnd((M, K), 1), rnd((N, K), 2, 0.05), rnd((N,), 3, 0.1), rnd((M, N), 4)
     want = ref.gemm(A, W, bias=b, residual=r_)
-    got = ops.gemm(A.cuda(), W.cuda(), bias=b.cuda(), residual=r_.cuda())
+    env = {"SVLM_GEMM_BM": bm, "SVLM_GEMM_SPLITS": splits}
+    with H.forced_switches(env):
+        got = diag.gemm(A.cuda(), W.cuda(), bias=b.cuda(), residual=r_.cuda())
+        plan = diag.last_gemm_plan()
+    exp = G.plan_bf16(M, N, K, env={k: str(v) for k, v in env.items()})
+    assert plan["bm"] == bm and plan["splits"] == exp["splits"] and (splits == 1 or plan["splits"] >= 2), plan
+    assert {k: plan[k] for k in ("bm", "waves", "stages", "dma", "splits", "kps", "table")} == {k: exp[k] for k in ("bm", "waves", "stages", "dma", "splits", "kps", "table")}
     close(f"gemm plan bm{bm} s{splits}", got, want)
 
 
@@ -117,19 +131,22 @@ def test_gemm_norm_fused_reduce(ops, ref, M, N, K):
 
 
 @pytest.mark.parametrize("M,I,K", [(290, 8960, 1536), (290, 18944, 3584), (590, 18944, 3584), (37, 104, 128), (130, 512, 256), (1, 64, 64), (2050, 192, 2048), (2048, 1792, 2048)])
-def test_gemm_swiglu_epilogue(ops, ref, M, I, K, monkeypatch):
+def test_gemm_swiglu_epilogue(ops, diag, ref, M, I, K):
     """ACT_SWIGLU: W = [gate rows; up rows]; every tile pairs 64 gate with the 64 matching up columns and applies
     bf16(bf16(silu(g)) * u) in its epilogue == GEMM to (M, 2I) followed by svlm_silu_mul, for both tile heights."""
     A, W = rnd((M, K), 1), rnd((2 * I, K), 2, 0.05)
     want = ref.gemm(A, W, act=4)
     gu = ops.gemm(A.cuda(), W.cuda())
     sep = ops.silu_mul(gu, out=torch.empty((M, I), dtype=BF16, device="cuda"))
+    import helpers as H
     for bm in (None, 64, 128):
         if bm is None:
-            monkeypatch.delenv("SVLM_GEMM_BM", raising=False)
-        else:
-            monkeypatch.setenv("SVLM_GEMM_BM", str(bm))
-        got = ops.gemm(A.cuda(), W.cuda(), act=4)
+            got = ops.gemm(A.cuda(), W.cuda(), act=4)
+        else:                          # forced tile heights: on the diagnostic library, which must report the forced tile
+            with H.forced_switches({"SVLM_GEMM_BM": bm}):
+                got = diag.gemm(A.cuda(), W.cuda(), act=4)
+                plan = diag.last_gemm_plan()
+            assert plan["bm"] == (bm if M > 64 else 64) and plan["splits"] == 1, plan
         assert got.shape == (M, I)
         close(f"gemm swiglu bm={bm}", got, want)
         # (the large-M case's separate (M, 2I) GEMM has too few tiles and splits K: another summation order)
