@@ -363,6 +363,28 @@ int svlm_decb_lm_head(const void* lanes, int B, const void* x, int ldx, const vo
                       int ldl, const int* suppress, void* ws, int V, int K, void* stream);
 int svlm_decb_argmax_finish(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream);
 
+/* ---- stream groups on fp8 language-model weights (csrc/decode_batch_fp8.hip): the lane-batched twins of the single-row fp8 entries
+ * above, with W8 + w_scale in place of W.  Per (lane, output row) every output is BITWISE what the single-row fp8 entry computes for
+ * the lane alone; each 16-code weight vector is converted to fp32 once for all B lanes.  Same lane table, same skipping of a lane
+ * that is not live.  B in 1..4, K and ldw multiples of 16, K <= 8192, B * K * 2 <= 65536 - 256 for the three entries that stage the
+ * normalised rows in LDS.  svlm_decb_embed (the embedding table stays bf16), svlm_decb_lm_head_ws_stride and
+ * svlm_decb_argmax_finish serve both weight formats.
+ * replaces: qwen2/language_forward.py:183,80-82 + generate/streaming_cache.py:72-73 (as svlm_dec_qkv_fp8).  head_dim 128. */
+int svlm_decb_qkv_fp8(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W8, int ldw,
+                      const float* w_scale, const void* bias, void* q_out, int ldq, int layer, int K, int qd, int kd, int D, void* stream);
+/* replaces: qwen2/language_forward.py:200-201 (Qwen2MLP gate/up + SwiGLU, as svlm_dec_gate_up_fp8). */
+int svlm_decb_gate_up_fp8(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W8, int ldw,
+                          const float* w_scale, void* h, int ldh, int I, int K, void* stream);
+/* svlm_gemv_fp8 with residual for B lanes: y[b] = bf16(bf16(W' x[b]) + residual[b]); y may be residual.  Every shape takes the form
+ * (rows per wave, K split over the waves) the single-row entry takes.
+ * replaces: o_proj / down_proj at T = 1 (qwen2/language_forward.py:161,201). */
+int svlm_decb_gemv_fp8(const void* lanes, int B, const void* x, int ldx, const void* W8, int ldw, const float* w_scale,
+                       const void* residual, int ldr, void* y, int ldy, int N, int K, void* stream);
+/* svlm_dec_lm_head_fp8 (greedy) for B lanes: the candidates in the layout svlm_decb_lm_head leaves, completed by svlm_decb_argmax_finish.
+ * replaces: qwen2/language_forward.py:315, qwen2/model_forward.py:243, generate/streaming_generate_qwen.py:73-104. */
+int svlm_decb_lm_head_fp8(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W8, int ldw,
+                          const float* w_scale, float* logits, int ldl, const int* suppress, void* ws, int V, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,10 @@ SIGNATURES = {
     "svlm_decb_lm_head_ws_stride": (_ll, [_i]),
     "svlm_decb_lm_head": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_decb_argmax_finish": (_i, [_p, _i, _p, _i, _i, _p]),
+    "svlm_decb_qkv_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "svlm_decb_gate_up_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "svlm_decb_gemv_fp8": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),
+    "svlm_decb_lm_head_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p]),
 }
 
 _lib = None

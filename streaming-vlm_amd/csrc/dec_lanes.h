@@ -1,0 +1,42 @@
+// The lane table and the activation-row prologue shared by the lane-batched decode kernels (decode_batch.hip: bf16 weights,
+// decode_batch_fp8.hip: e4m3 weights).
+#pragma once
+#include "common.h"
+#include "dec_xrow.h"
+
+struct svlm_lane {                 // mirror of include/svlm.h
+  bf16_t* pool;                    // [n_layers][2][Hkv][n_slots][D]
+  bf16_t* lin;                     // [n_layers][2][Hkv][lin_rows][D] or null
+  const int* slot_of;
+  int* state;                      // {kv_len, cur}
+  int* tok_buf;
+  unsigned char* seen;             // [V] or null (no repetition penalty)
+  int limit;                       // live while state[1] + 1 < limit
+  int n_slots;
+  int lin_rows;
+  float penalty;
+  int n_suppress;
+  int pad_;
+};
+static_assert(sizeof(svlm_lane) == 72, "svlm_lane layout (include/svlm.h)");
+
+__device__ __forceinline__ bool lane_live(const svlm_lane& L) { return L.state[1] + 1 < L.limit; }
+
+// Prologue of the fused kernels: the live lanes' x rows are requested first, then the head of the weight stream, then the rows are
+// normalised and staged one after the other (xs[b * K ..]); a lane that is not live leaves its LDS row as it is (its products are
+// never written).
+template <int NB, int XC>
+__device__ __forceinline__ void load_rows(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                          const bf16_t* __restrict__ ln_w, int K, XRow<XC> (&xr)[NB], bool (&live)[NB]) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    live[b] = lane_live(lanes[b]);
+    if (live[b]) load_x<XC>(x + (size_t)b * ldx, ln_w, K, xr[b]);
+  }
+}
+template <int NB, int XC>
+__device__ __forceinline__ void stage_rows(const XRow<XC> (&xr)[NB], const bool (&live)[NB], float eps, int K, bf16_t* xs) {
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+    if (live[b]) stage_x<XC>(xr[b], eps, K, xs + (size_t)b * K);          // (workgroup-uniform branch: barriers inside)
+}

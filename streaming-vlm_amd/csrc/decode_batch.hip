@@ -25,24 +25,7 @@
 #include "common.h"
 #include "dec_xrow.h"
 #include "dec_stream.h"
-
-struct svlm_lane {                 // mirror of include/svlm.h
-  bf16_t* pool;                    // [n_layers][2][Hkv][n_slots][D]
-  bf16_t* lin;                     // [n_layers][2][Hkv][lin_rows][D] or null
-  const int* slot_of;
-  int* state;                      // {kv_len, cur}
-  int* tok_buf;
-  unsigned char* seen;             // [V] or null (no repetition penalty)
-  int limit;                       // live while state[1] + 1 < limit
-  int n_slots;
-  int lin_rows;
-  float penalty;
-  int n_suppress;
-  int pad_;
-};
-static_assert(sizeof(svlm_lane) == 72, "svlm_lane layout (include/svlm.h)");
-
-__device__ __forceinline__ bool lane_live(const svlm_lane& L) { return L.state[1] + 1 < L.limit; }
+#include "dec_lanes.h"            // svlm_lane, lane_live, load_rows, stage_rows: shared with decode_batch_fp8.hip
 
 // acc[b][r] += W[row r] . xs[b] over the PRE K-steps held in `pre`; per (b, r) the same FMA sequence as fma_batch (decode_fused.hip)
 template <int NB, int NR, int PRE>
@@ -87,25 +70,6 @@ __device__ __forceinline__ void wave_dots_b(const bf16_t* const (&wr)[NR], const
   for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int r = 0; r < NR; ++r) acc[b][r] = wave_sum(acc[b][r]);
-}
-
-// Prologue of the fused kernels: the live lanes' x rows are requested first, then the head of the weight stream, then the rows are
-// normalised and staged one after the other (xs[b * K ..]); a lane that is not live leaves its LDS row as it is (its products are
-// never written).
-template <int NB, int XC>
-__device__ __forceinline__ void load_rows(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
-                                          const bf16_t* __restrict__ ln_w, int K, XRow<XC> (&xr)[NB], bool (&live)[NB]) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    live[b] = lane_live(lanes[b]);
-    if (live[b]) load_x<XC>(x + (size_t)b * ldx, ln_w, K, xr[b]);
-  }
-}
-template <int NB, int XC>
-__device__ __forceinline__ void stage_rows(const XRow<XC> (&xr)[NB], const bool (&live)[NB], float eps, int K, bf16_t* xs) {
-#pragma unroll
-  for (int b = 0; b < NB; ++b)
-    if (live[b]) stage_x<XC>(xr[b], eps, K, xs + (size_t)b * K);          // (workgroup-uniform branch: barriers inside)
 }
 
 // ---------------------------------------------------------------- embedding gather

@@ -17,56 +17,9 @@
 // subnormals included) feeding the same fp32 FMAs the bf16 path sums with.
 #include "common.h"
 #include "dec_xrow.h"
-
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef uint8_t fp8_t;
-
-// the 16 bf16 activations of one lane's K-step, as fp32 (zero past K)
-__device__ __forceinline__ void x16(const bf16_t* xs, int c, int K, float (&xf)[16]) {
-  const int cc = c < K ? c : 0;
-  const u32x4_t a = *reinterpret_cast<const u32x4_t*>(xs + cc);
-  const u32x4_t b = *reinterpret_cast<const u32x4_t*>(xs + cc + 8);
-  float lo[8], hi[8];
-  unpack8(a, lo);
-  unpack8(b, hi);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    xf[i] = c < K ? lo[i] : 0.f;
-    xf[8 + i] = c < K ? hi[i] : 0.f;
-  }
-}
-
-// acc += sum_j e4m3(w byte j) * xf[j], in element order
-__device__ __forceinline__ float dot16(const u32x4_t& w, const float (&xf)[16], float acc) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
-    const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
-    acc = fmaf(lo[0], xf[4 * i], acc);
-    acc = fmaf(lo[1], xf[4 * i + 1], acc);
-    acc = fmaf(hi[0], xf[4 * i + 2], acc);
-    acc = fmaf(hi[1], xf[4 * i + 3], acc);
-  }
-  return acc;
-}
+#include "dec_fp8.h"              // x16, dot16, W8Pre, preload_w8: shared with decode_batch_fp8.hip
 
 // ---------------------------------------------------------------- fused decode kernels (x staged in LDS)
-template <int NR, int PRE>
-struct W8Pre {
-  u32x4_t w[PRE][NR];
-};
-template <int NR, int PRE>
-__device__ __forceinline__ void preload_w8(const fp8_t* const (&wr)[NR], int base, int K, W8Pre<NR, PRE>& pre) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int it = 0; it < PRE; ++it) {
-    const int c = base + it * 1024 + lane * 16;
-    const int cc = c < K ? c : 0;                            // clamped (valid) address; its product is masked out
-#pragma unroll
-    for (int r = 0; r < NR; ++r) pre.w[it][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr[r] + cc));
-  }
-}
-
 template <int NR, int PRE>
 __device__ __forceinline__ void fma_batch8(const W8Pre<NR, PRE>& pre, const bf16_t* xs, int base, int K, float (&acc)[NR]) {
   const int lane = threadIdx.x & 63;

@@ -251,7 +251,10 @@ class SvlmEngine:
                  vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None):
         """`share`: another engine of the same model whose WEIGHTS this one uses (language model, vision tower, embedding, lm_head,
         rope frequencies, fp8 vision images): `state_dict` is ignored and no weight tensor is copied; every per-stream buffer (sampling
-        state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py)."""
+        state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py).
+        With `llm_fp8` the engines that share weights also share the ONE bf16 scratch layer the prefill dequantises into, so they must
+        prefill one after another, as a stream group does; a prefill issued on another stream than the last one waits for that stream
+        first (`_dequant_layer`), two prefills issued concurrently from two host threads are not supported."""
         if share is not None:
             if share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8:
                 raise ValueError("share=: the engines must agree on model config, device, llm_fp8 and vit_fp8")
@@ -277,6 +280,9 @@ class SvlmEngine:
                 raise ValueError("llm_fp8=True cannot be combined with decode_tail=True (the persistent layer tail streams bf16 weights)")
         self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8)
         self._fp8_scratch = None           # llm_fp8: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
+        self._fp8_scratch_owner = share._fp8_scratch_owner if share is not None else self      # whose scratch layer this engine uses
+        if share is not None:
+            self._fp8_scratch_owner._fp8_scratch_shared = True
         tc, vc = cfg.text, cfg.vision
         if tc.head_dim != 128 or sum(tc.mrope_section) * 2 != tc.head_dim:
             raise ValueError("LLM head_dim must be 128 with mrope sections summing to 64")
@@ -604,7 +610,19 @@ class SvlmEngine:
 
     def _dequant_layer(self, lw):
         """llm_fp8 prefill: the layer's four matrices as bf16 W' in the (reused) scratch layer; the layer dict with those views."""
-        sc = self._fp8_scratch
+        # Engines that share weights (share=: the lanes of a stream group) share the ONE scratch layer of the engine that owns the
+        # weights.  That is safe because a group's prefills never overlap: `StreamGroup.generate` calls the lanes' `generate_begin`
+        # one after another from the one thread that issues the batch, every launch of a prefill -- the dequantisation and the GEMMs
+        # that read it -- goes to that thread's current stream, and the look-ahead vision stream never touches the language model,
+        # so stream order alone keeps lane k + 1's dequantisation behind lane k's last GEMM.
+        own = self._fp8_scratch_owner
+        if getattr(own, "_fp8_scratch_shared", False) and self.device.type == "cuda":
+            # a caller that does move to another stream: the new stream first waits for everything the last user queued on its own
+            stream, last = torch.cuda.current_stream(self.device), getattr(own, "_fp8_scratch_stream", None)
+            if last is not None and last != stream:
+                stream.wait_stream(last)
+            own._fp8_scratch_stream = stream
+        sc = self._fp8_scratch = own._fp8_scratch
         if sc is None:
             flat = torch.empty(lw["flat8"].numel(), dtype=BF16, device=self.device)
             sc, off = {}, 0
@@ -612,7 +630,7 @@ class SvlmEngine:
                 n = lw[name + "8"].numel()
                 sc[name] = flat[off:off + n].view(lw[name + "8"].shape)
                 off += n
-            self._fp8_scratch = sc
+            self._fp8_scratch = own._fp8_scratch = sc
         for name, dst in sc.items():
             self.ops.dequant_fp8(lw[name + "8"], lw[name + "_s"], dst)
         return dict(lw, **sc)

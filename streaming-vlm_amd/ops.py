@@ -733,6 +733,43 @@ class HipOps:
         assert ws.is_contiguous() and ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
         self._check(self.lib.svlm_decb_argmax_finish(_ptr(lanes), B, _ptr(ws), V, int(advance_kv), _stream()), "svlm_decb_argmax_finish")
 
+    # the same on e4m3 weights with per-row scales (csrc/decode_batch_fp8.hip): (W8, w_scale) where W stands; decb_embed,
+    # decb_sampling_ws and decb_argmax_finish serve both
+    def decb_qkv_fp8(self, lanes, B, x, ln_w, eps, W8, w_scale, bias, q_out, layer, qd, kd, D, n_layers):
+        self._lanes(lanes, B, "decb_qkv_fp8"); _req(ln_w, BF16, "decb_qkv_fp8.ln_w", 1); _req(bias, BF16, "decb_qkv_fp8.bias", 1)
+        N, K = self._req_fp8(W8, w_scale, "decb_qkv_fp8")
+        assert N == qd + 2 * kd == bias.numel() and ln_w.numel() == K and 0 <= layer < n_layers
+        ldx, ldq = self._rows(x, B, K, "decb_qkv_fp8.x"), self._rows(q_out, B, qd, "decb_qkv_fp8.q_out")
+        self._check(self.lib.svlm_decb_qkv_fp8(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias),
+                                         _ptr(q_out), ldq, int(layer), K, qd, kd, D, _stream()), "svlm_decb_qkv_fp8")
+
+    def decb_gate_up_fp8(self, lanes, B, x, ln_w, eps, W8, w_scale, h):
+        self._lanes(lanes, B, "decb_gate_up_fp8"); _req(ln_w, BF16, "decb_gate_up_fp8.ln_w", 1)
+        N, K = self._req_fp8(W8, w_scale, "decb_gate_up_fp8")
+        assert N % 2 == 0 and ln_w.numel() == K
+        ldx, ldh = self._rows(x, B, K, "decb_gate_up_fp8.x"), self._rows(h, B, N // 2, "decb_gate_up_fp8.h")
+        self._check(self.lib.svlm_decb_gate_up_fp8(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(h),
+                                             ldh, N // 2, K, _stream()), "svlm_decb_gate_up_fp8")
+
+    def decb_gemv_fp8(self, lanes, B, x, W8, w_scale, residual, out):
+        self._lanes(lanes, B, "decb_gemv_fp8")
+        N, K = self._req_fp8(W8, w_scale, "decb_gemv_fp8")
+        ldx, ldr = self._rows(x, B, K, "decb_gemv_fp8.x"), self._rows(residual, B, N, "decb_gemv_fp8.residual")
+        ldy = self._rows(out, B, N, "decb_gemv_fp8.out")
+        self._check(self.lib.svlm_decb_gemv_fp8(_ptr(lanes), B, _ptr(x), ldx, _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(residual), ldr, _ptr(out),
+                                          ldy, N, K, _stream()), "svlm_decb_gemv_fp8")
+
+    def decb_lm_head_fp8(self, lanes, B, x, ln_w, eps, W8, w_scale, logits, suppress, ws):
+        """decb_lm_head on e4m3 rows: the same candidates in `ws`, completed by decb_argmax_finish."""
+        self._lanes(lanes, B, "decb_lm_head_fp8"); _req(ln_w, BF16, "decb_lm_head_fp8.ln_w", 1)
+        _req(suppress, torch.int32, "decb_lm_head_fp8.suppress", 1); _req(ws, torch.float32, "decb_lm_head_fp8.ws", 2)
+        V, K = self._req_fp8(W8, w_scale, "decb_lm_head_fp8")
+        assert ln_w.numel() == K and suppress.numel() >= 8 and ws.is_contiguous()
+        assert ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        ldx, ldl = self._rows(x, B, K, "decb_lm_head_fp8.x"), self._rows(logits, B, V, "decb_lm_head_fp8.logits", torch.float32)
+        self._check(self.lib.svlm_decb_lm_head_fp8(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale),
+                                             _ptr(logits), ldl, _ptr(suppress), _ptr(ws), V, K, _stream()), "svlm_decb_lm_head_fp8")
+
     # ------------------------------------------------------------------ fp8 language-model weights (csrc/decode_fp8.hip)
     @staticmethod
     def _req_fp8(W8, scale, name):

@@ -1,5 +1,8 @@
 """Stream groups: B independent streams (B = 1..4, "lanes") on one GPU and ONE weight set, whose decode steps run in lock-step through
 the lane-batched kernels of csrc/decode_batch.hip -- each weight byte is read once and each launch boundary paid once for B tokens.
+An `llm_fp8=True` engine takes the same steps through the e4m3 twins of csrc/decode_batch_fp8.hip: half the weight bytes, read once
+for B tokens, and each weight converted to fp32 once for all B lanes.  Its prefill stays per stream and dequantises layer by layer
+into ONE bf16 scratch layer that all lanes share (a group pays that dequantisation once per lane and chunk).
 
 A lane is an `SvlmEngine` that shares the group engine's weights (`SvlmEngine(share=...)`; lane 0 IS the group engine) and owns
 everything a stream owns: KV pool, positions, rope table, sampling state, eviction history.  `StreamGroup.generate` runs
@@ -8,7 +11,7 @@ lane; per lane the tokens, cache length and logical order are EXACTLY those of t
 the single-row ones per lane, and the decode attention is the unchanged single-stream kernel, launched once per lane).
 
 Opt-in; nothing here is reached by the single-stream path.  Refused with a ValueError instead of silently falling back:
-`llm_fp8=True` and `decode_tail=True` engines, `do_sample=True` with anything but `top_k == 1`, `force_tokens`, `keep_logits`.
+`decode_tail=True` engines, an `llm_fp8=True` engine whose ops backend lacks the batched fp8 entry points, `do_sample=True` with anything but `top_k == 1`, `force_tokens`, `keep_logits`.
 The look-ahead ViT (`next_vision`) is DECLINED: a group runs strict-causal, every chunk's vision tower runs inside its own
 `generate_begin`.
 """
@@ -31,6 +34,8 @@ MAX_LANES = 4
 # aggregate frames/s stops growing at 3 lanes on Qwen2-VL-2B (profiles/stream_group_2b.json: 4 lanes are 0.6 % below 3), so nothing picks
 # more than 3 by itself; 4 remain available on request
 DEFAULT_LANES = 3
+# ops entry points a group on an llm_fp8 engine needs (csrc/decode_batch_fp8.hip)
+FP8_GROUP_OPS = ("decb_qkv_fp8", "decb_gate_up_fp8", "decb_gemv_fp8", "decb_lm_head_fp8")
 
 
 def check_request(req: dict) -> dict:
@@ -147,7 +152,10 @@ class StreamGroup:
         if not 1 <= int(n_lanes) <= MAX_LANES:
             raise ValueError(f"n_lanes={n_lanes} outside [1, {MAX_LANES}]")
         if getattr(engine, "llm_fp8", False):
-            raise ValueError("stream group: llm_fp8=True engines are not supported (the lane-batched kernels stream bf16 weights)")
+            missing = [m for m in FP8_GROUP_OPS if not hasattr(getattr(engine, "ops", None), m)]
+            if missing:
+                raise ValueError(f"stream group: an llm_fp8=True engine needs an ops backend with the lane-batched fp8 entry points; "
+                                 f"{type(getattr(engine, 'ops', None)).__name__} lacks {missing}")
         if getattr(engine, "decode_tail", False):
             raise ValueError("stream group: decode_tail=True engines are not supported (the persistent layer tail is single-row)")
         self.engine = engine
@@ -156,7 +164,8 @@ class StreamGroup:
         self.lanes: List[SvlmEngine] = [engine] + [
             SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
                        use_graph=engine.use_graph, kv_slack=engine.kv_slack, kv_page_tokens=engine.kv_page_tokens, decode_tail=False,
-                       vit_fp8=engine.vit_fp8, linear_planes=engine.linear_planes, share=engine) for _ in range(self.n_lanes - 1)]
+                       vit_fp8=engine.vit_fp8, linear_planes=engine.linear_planes, llm_fp8=engine.llm_fp8, share=engine)
+            for _ in range(self.n_lanes - 1)]
         for ln in self.lanes[1:]:
             ln.default_top_k, ln.default_top_p, ln.eos_dev = engine.default_top_k, engine.default_top_p, engine.eos_dev
         B, H, V = self.n_lanes, tc.hidden_size, tc.vocab_size
@@ -207,6 +216,9 @@ class StreamGroup:
         scale = 1.0 / math.sqrt(tc.head_dim)
         tab = self.table
         o.decb_embed(tab, B, w.embed, self.x)
+        if e.llm_fp8:
+            self._layers_and_head_fp8(act, tab, B, scale)
+            return
         for li, lw in enumerate(w.layers):
             o.decb_qkv(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
             for j, (lane, c) in enumerate(act):          # the single-stream attention, once per lane, same stream (no forked branches)
@@ -216,6 +228,22 @@ class StreamGroup:
             o.decb_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
             o.decb_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
         o.decb_lm_head(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
+        o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
+
+    def _layers_and_head_fp8(self, act, tab, B, scale):
+        """The layers and the head of `_step_launch` on e4m3 weights: the same launches with the four weight-streaming kernels replaced by
+        their fp8 twins (csrc/decode_batch_fp8.hip)."""
+        e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
+        qd, kd, nl = e.qd, e.kd, len(w.layers)
+        for li, lw in enumerate(w.layers):
+            o.decb_qkv_fp8(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w8"], lw["qkv_w_s"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
+            for j, (lane, c) in enumerate(act):
+                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
+                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            o.decb_gemv_fp8(tab, B, self.attn, lw["o_w8"], lw["o_w_s"], self.x, self.x)
+            o.decb_gate_up_fp8(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w8"], lw["gu_w_s"], self.h)
+            o.decb_gemv_fp8(tab, B, self.h, lw["down_w8"], lw["down_w_s"], self.x, self.x)
+        o.decb_lm_head_fp8(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, self.suppress, self.ws)
         o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
 
     def _step(self, idx, act):

@@ -9,10 +9,16 @@ Passes, each after its own warm-up (KV window filled, graphs captured), each tim
 and, per B, the decode steps alone: `--steps`-fold replay of the captured batched step (19 steps = one chunk's decode) against the
 single-stream step graph.
 
+`--llm-fp8`: the model is built with llm_fp8=True (e4m3 language-model weights) and takes the same passes through the lane-batched fp8
+kernels (csrc/decode_batch_fp8.hip); the bf16 group passes of the same weights run in the same process ("group_bf16"), so the fp8 group
+is read against the bf16 group and the solo fp8 stream of ONE run, never against a profile of another day.
+
 Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- python tools/stream_group_bench.py --kernels-only`
 (a run of its own, no counters) and pass the stats CSV with --kernel-stats to have the decb_* / single-row averages folded in.
 
     python tools/stream_group_bench.py --out profiles/stream_group_2b.json
+    python tools/stream_group_bench.py --llm-fp8                                      (writes profiles/stream_group_fp8_2b.json)
+    python tools/stream_group_bench.py --llm-fp8 --model 7b --fps 2 --window 4096     (writes profiles/stream_group_fp8_7b.json)
 """
 import argparse
 import csv
@@ -33,6 +39,44 @@ from streaming_vlm_amd.synthetic import ResidentProcessor, ResidentVideo  # noqa
 from streaming_vlm_amd.weights import random_state_dict  # noqa: E402
 
 
+def weight_bytes(kernel, tc):
+    """Weight bytes one launch of a lane-batched (decb_*) kernel streams, from its name: e4m3 codes + fp32 row scales for the fp8 twins,
+    bf16 otherwise.  The residual GEMV that splits K over the waves (down_proj) is told from the plain one (o_proj) by its name / KW."""
+    import re
+    if "decb_" not in kernel or "embed" in kernel or "argmax" in kernel:
+        return 0
+    H, I, qd, kd = tc.hidden_size, tc.intermediate_size, tc.num_heads * tc.head_dim, tc.num_kv_heads * tc.head_dim
+    fp8 = "_fp8" in kernel
+    if "qkv" in kernel:
+        n, k = qd + 2 * kd, H
+    elif "gate_up" in kernel:
+        n, k = 2 * I, H
+    elif "lm_head" in kernel:
+        n, k = tc.vocab_size, H
+    elif "gemv" in kernel:
+        m = re.search(r"<\s*\d+\s*,\s*\d+\s*,\s*(\d+)\s*,", kernel)
+        split = "ksplit" in kernel or (fp8 and m is not None and m.group(1) == "4")
+        n, k = (H, I) if split else (H, qd)
+    else:
+        return 0
+    return n * k + 4 * n if fp8 else 2 * n * k
+
+
+def kernel_stats(path, cfg):
+    """The decode kernels' rows of a rocprofv3 kernel_stats CSV: calls, average us and, for the lane-batched GEMVs, TB/s on their weight bytes."""
+    rows = {}
+    for r in csv.DictReader(open(path)):
+        name = r.get("Name") or r.get("KernelName") or ""
+        if any(k in name for k in ("decb_", "dec_qkv_kernel", "dec_gate_up_kernel", "dec_lm_head_kernel", "gemv_bf16", "argmax_finish", "decode_attn",
+                                   "dec_qkv_fp8", "dec_gate_up_fp8", "dec_lm_head_fp8", "gemv_fp8", "dequant_fp8")):
+            rec = rows[name[:120]] = dict(calls=int(r["Calls"]), avg_us=float(r["AverageNs"]) / 1e3)
+            nbytes = weight_bytes(name, cfg.text)
+            if nbytes:
+                rec["weight_bytes"] = nbytes
+                rec["weight_tb_per_s"] = nbytes / (rec["avg_us"] * 1e-6) / 1e12
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="2b", choices=["2b", "7b", "tiny"])
@@ -44,20 +88,34 @@ def main():
     ap.add_argument("--steps", type=int, default=40, help="timed chunks per pass")
     ap.add_argument("--repeats", type=int, default=3, help="single-stream passes (noise estimate)")
     ap.add_argument("--max-lanes", type=int, default=4)
+    ap.add_argument("--llm-fp8", action="store_true", help="e4m3 language-model weights: fp8 solo + fp8 groups, and the bf16 groups of the same run")
     ap.add_argument("--kernels-only", action="store_true", help="one short pass per B and nothing else (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 kernel_stats CSV of a --kernels-only run")
-    ap.add_argument("--out", default=None)
+    ap.add_argument("--fold", default=None, help="with --kernel-stats: add the kernel averages to this earlier record of the same workload "
+                                                 "and write it to --out; no GPU work")
+    ap.add_argument("--out", default=None, help="record file; --llm-fp8 timed runs default to profiles/stream_group_fp8_<model>.json")
     args = ap.parse_args()
+    if args.llm_fp8 and not args.kernels_only and not args.fold and args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"stream_group_fp8_{args.model}.json")
 
-    dev = torch.device("cuda", 0)
     cfg = {"2b": C.qwen2_vl_2b, "7b": C.qwen2_vl_7b, "tiny": C.tiny}[args.model]()
+    if args.fold:
+        if not args.kernel_stats:
+            ap.error("--fold needs --kernel-stats")
+        out = json.load(open(args.fold))
+        out["kernel_stats"] = kernel_stats(args.kernel_stats, cfg)
+        with open(args.out or args.fold, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+        return
+    dev = torch.device("cuda", 0)
     tok_per_frame = (args.size // 28) ** 2
     chunk_tokens = tok_per_frame + 24 + args.new_tokens
     max_len = args.sink + args.window + 2 * chunk_tokens + 64
     fill = -(-(args.sink + args.window) // (tok_per_frame + 19 + args.new_tokens)) + 2
     steps = 6 if args.kernels_only else args.steps
     n_chunks = fill + steps
-    model = S.StreamingQwen2VL(cfg, random_state_dict(cfg, 0, dev), dev, max_len=max_len, max_new_tokens=args.new_tokens)
+    sd = random_state_dict(cfg, 0, dev)
+    model = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens, llm_fp8=args.llm_fp8)
     eng = model._svlm_engine
     base = "Qwen2"
     torch.set_num_threads(min(torch.get_num_threads(), 8))
@@ -117,27 +175,43 @@ def main():
                            frames_per_sec_median=statistics.median(p["frames_per_sec"] for p in solo))
         out["solo_lookahead"] = timed(solo_run, 1, True)
         out["solo"]["decode_ms_per_chunk"] = replay_decode(eng._graph, [eng], args.new_tokens - 1)       # (its cache is still eng._last_cache)
-    groups = {}
-    for B in range(1, args.max_lanes + 1):
-        group = StreamGroup(eng, B)
-        rec = timed(lambda kws: S.streaming_inference_group(model, proc, kws, group=group), B, False)
-        # the decode steps alone: the batched step graph of the last batch, one chunk's worth of replays per round
-        rec["decode_ms_per_chunk"] = replay_decode(next(reversed(group._graphs.values()))[0], group.lanes, args.new_tokens - 1)
-        rec["decode_us_per_step"] = 1e3 * rec["decode_ms_per_chunk"] / (args.new_tokens - 1)
-        groups[str(B)] = rec
-        del group
-    out["group"] = groups
+
+    def group_passes(m):
+        groups = {}
+        for B in range(1, args.max_lanes + 1):
+            group = StreamGroup(m._svlm_engine, B)
+            rec = timed(lambda kws: S.streaming_inference_group(m, proc, kws, group=group), B, False)
+            # the decode steps alone: the batched step graph of the last batch, one chunk's worth of replays per round
+            rec["decode_ms_per_chunk"] = replay_decode(next(reversed(group._graphs.values()))[0], group.lanes, args.new_tokens - 1)
+            rec["decode_us_per_step"] = 1e3 * rec["decode_ms_per_chunk"] / (args.new_tokens - 1)
+            groups[str(B)] = rec
+            del group
+        return groups
+
+    groups = out["group"] = group_passes(model)
+    out["llm_fp8"] = bool(args.llm_fp8)
+    out["decode_weight_bytes"] = eng.w.decode_bytes()
     if "solo" in out:
         ref = out["solo"]["frames_per_sec_median"]
         for B, rec in groups.items():
             rec["aggregate_frames_per_sec_vs_solo"] = rec["frames_per_sec"] / ref
+    if args.llm_fp8:
+        # the bf16 groups of the same weights, same process, same run: what the fp8 groups are read against
+        bf = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens)
+        gb = out["group_bf16"] = group_passes(bf)
+        out["decode_weight_bytes_bf16"] = bf._svlm_engine.w.decode_bytes()
+        for B, rec in groups.items():
+            rec["decode_step_vs_bf16_group"] = rec["decode_us_per_step"] / gb[B]["decode_us_per_step"]
+            rec["frames_per_sec_vs_bf16_group"] = rec["frames_per_sec"] / gb[B]["frames_per_sec"]
+        best = lambda g: max(g, key=lambda B: g[B]["frames_per_sec"])
+        out["best"] = dict(fp8_lanes=int(best(groups)), fp8_frames_per_sec=groups[best(groups)]["frames_per_sec"],
+                           bf16_lanes=int(best(gb)), bf16_frames_per_sec=gb[best(gb)]["frames_per_sec"])
+        if "solo" in out:
+            # the only margin: the solo repeats' own spread, as frames/s
+            fps_solo = [p["frames_per_sec"] for p in out["solo"]["passes"]]
+            out["best"].update(solo_fp8_frames_per_sec=ref, solo_fp8_frames_per_sec_spread=max(fps_solo) - min(fps_solo))
     if args.kernel_stats:
-        rows = {}
-        for r in csv.DictReader(open(args.kernel_stats)):
-            name = r.get("Name") or r.get("KernelName") or ""
-            if any(k in name for k in ("decb_", "dec_qkv_kernel", "dec_gate_up_kernel", "dec_lm_head_kernel", "gemv_bf16", "argmax_finish", "decode_attn")):
-                rows[name[:120]] = dict(calls=int(r["Calls"]), avg_us=float(r["AverageNs"]) / 1e3)
-        out["kernel_stats"] = rows
+        out["kernel_stats"] = kernel_stats(args.kernel_stats, cfg)
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
