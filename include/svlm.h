@@ -318,6 +318,19 @@ int svlm_dec_lm_head_sample_fp8(const void* x, const void* ln_w, float eps, cons
 /* dst[r, c] = bf16(src8[r, c] * scale[r]) for contiguous [rows, cols] matrices (cols a multiple of 16): the bf16 image W' of one layer,
  * which the prefill GEMMs read.  replaces: nothing (the reference has bf16 weights; this rebuilds them from the fp8 copy). */
 int svlm_dequant_fp8_bf16(const void* src8, const float* scale, void* dst, int rows, int cols, void* stream);
+/* svlm_gemm_bf16 / svlm_gemm_bf16_norm on W' = W8 * w_scale read straight from the e4m3 codes (csrc/gemm_wfp8.hip): A stays bf16, W8 is
+ * N rows (2N for SVLM_ACT_SWIGLU, [gate; up]) of ldw BYTES, w_scale one power-of-two scale per row of W8 in the same order.  The codes are
+ * staged at half the bytes of the bf16 image and converted (code * scale, exact in bf16) where a wave reads its MFMA fragment, so the
+ * products, their order and the whole epilogue (bias, act 0..4, residual incl. in place, split-K through ws, the norm in the split-K
+ * reduce) are those of svlm_gemm_bf16 on the dequantised matrix; with the same K per split the two are equal bit for bit.  K % 64 == 0,
+ * ldw % 16 == 0 and W8 16-B aligned, else SVLM_EINVAL.  Tile and split selection is this entry's own.
+ * replaces: the prefill-row Linears of svlm_gemm_bf16 (qwen2/language_forward.py:80-82,161,201) for an fp8 language model, and the
+ * svlm_dequant_fp8_bf16 launch in front of each (`SvlmEngine(llm_fp8=True, prefill_fp8=True)`). */
+int svlm_gemm_wfp8(const void* A, int lda, const void* W8, int ldw, const float* w_scale, const void* bias, const void* residual, int ldr,
+                   void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, void* stream);
+int svlm_gemm_wfp8_norm(const void* A, int lda, const void* W8, int ldw, const float* w_scale, const void* bias, const void* residual,
+                        int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, const void* norm_w,
+                        const void* norm_b, float eps, void* XN, int ldxn, void* stream);
 
 /* ---- stream groups: lane-batched decode step (csrc/decode_batch.hip; stream_group.py).  B = 1..4 independent streams ("lanes") on
  * one GPU and ONE weight set take their decode step together: every kernel below reads each weight row once and multiplies it with the

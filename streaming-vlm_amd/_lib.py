@@ -79,6 +79,8 @@ SIGNATURES = {
     "svlm_dec_lm_head_fp8": (_i, [_p, _p, _f, _p, _i, _p, _p, _p, _f, _p, _i, _p, _i, _i, _p]),
     "svlm_dec_lm_head_sample_fp8": (_i, [_p, _p, _f, _p, _i, _p, _p, _p, _f, _p, _i, _p, _i, _i, _f, _p, _p, _p]),
     "svlm_dequant_fp8_bf16": (_i, [_p, _p, _p, _i, _i, _p]),
+    "svlm_gemm_wfp8": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "svlm_gemm_wfp8_norm": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _f, _p, _i, _p]),
     "svlm_decb_embed": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
     "svlm_decb_qkv": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "svlm_decb_gate_up": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p]),

@@ -584,8 +584,8 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
                      void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, void* stream,
                      const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn);
 #ifdef SVLM_TUNING
-// What the last svlm_gemm_bf16* / svlm_gemm_fp8* call of this process launched (diagnostic library only, see common.h).
-// out[0..9] = {calls so far, 1 for the fp8 GEMM, tile rows, waves, ring stages, 1 = LDS-DMA / 0 = register-staged, live K-splits,
+// What the last svlm_gemm_bf16* / svlm_gemm_fp8* / svlm_gemm_wfp8* call of this process launched (diagnostic library only, see common.h).
+// out[0..9] = {calls so far, 1 for the fp8 GEMM / 2 for the weight-fp8 GEMM (gemm_wfp8.hip), tile rows, waves, ring stages, 1 = LDS-DMA / 0 = register-staged, live K-splits,
 // K per split, 1 = a tuned-table entry set the plan, 1 = the norm rode in the split-K reduce}; returns how many it wrote.
 SvlmGemmPlanNote g_svlm_gemm_plan_note = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 extern "C" int svlm_diag_last_gemm_plan(int* out, int n) {

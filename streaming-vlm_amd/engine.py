@@ -32,6 +32,8 @@ from .weights import EngineWeights
 BF16 = torch.bfloat16
 # ops entry points an llm_fp8 engine needs (csrc/decode_fp8.hip)
 FP8_LLM_OPS = ("dec_qkv_fp8", "dec_gate_up_fp8", "gemv_fp8", "dec_lm_head_fp8", "dequant_fp8")
+# ... and a prefill_fp8 engine on top of them (csrc/gemm_wfp8.hip)
+FP8_PREFILL_OPS = ("gemm_wfp8", "gemm_wfp8_norm")
 
 
 @dataclass
@@ -248,16 +250,20 @@ class SvlmEngine:
     def __init__(self, cfg: ModelConfig, state_dict, device="cuda", ops=None, max_len: int = 4096, max_new_tokens: int = 32,
                  decode_chunk: Optional[int] = None, use_graph: Optional[bool] = None, kv_slack: float = 1.0, kv_page_tokens: int = 16,
                  decode_tail: Optional[bool] = None,
-                 vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None):
+                 vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None,
+                 prefill_fp8: bool = False):
         """`share`: another engine of the same model whose WEIGHTS this one uses (language model, vision tower, embedding, lm_head,
         rope frequencies, fp8 vision images): `state_dict` is ignored and no weight tensor is copied; every per-stream buffer (sampling
         state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py).
         With `llm_fp8` the engines that share weights also share the ONE bf16 scratch layer the prefill dequantises into, so they must
         prefill one after another, as a stream group does; a prefill issued on another stream than the last one waits for that stream
-        first (`_dequant_layer`), two prefills issued concurrently from two host threads are not supported."""
+        first (`_dequant_layer`), two prefills issued concurrently from two host threads are not supported.
+        `prefill_fp8` (with `llm_fp8`): the prefill GEMMs read the e4m3 matrices themselves (`gemm_wfp8`, csrc/gemm_wfp8.hip): no
+        dequantisation launch, no scratch layer, nothing shared between the prefills of engines that share weights."""
         if share is not None:
-            if share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8:
-                raise ValueError("share=: the engines must agree on model config, device, llm_fp8 and vit_fp8")
+            if (share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8
+                    or bool(prefill_fp8) != share.prefill_fp8):
+                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, prefill_fp8 and vit_fp8")
             ops = share.ops if ops is None else ops
         if ops is None:
             from .ops import HipOps
@@ -278,6 +284,19 @@ class SvlmEngine:
                 raise ValueError(f"llm_fp8=True needs an ops backend with the fp8 entry points; {type(ops).__name__} lacks {missing}")
             if decode_tail or (decode_tail is None and os.environ.get("SVLM_DECODE_TAIL", "0") == "1"):
                 raise ValueError("llm_fp8=True cannot be combined with decode_tail=True (the persistent layer tail streams bf16 weights)")
+        # opt-in on top of llm_fp8: the prefill's four GEMMs per layer run on the e4m3 codes and their row scales (ops.gemm_wfp8*), which
+        # feed the MFMAs the operands the scratch layer would hold -- the same model W', without `dequant_fp8` and without the scratch layer
+        self.prefill_fp8 = bool(prefill_fp8)
+        if self.prefill_fp8:
+            if not self.llm_fp8:
+                raise ValueError("prefill_fp8=True needs llm_fp8=True (it is the prefill of the fp8 language-model weights)")
+            missing = [m for m in FP8_PREFILL_OPS if not hasattr(ops, m)]
+            if missing:
+                raise ValueError(f"prefill_fp8=True needs an ops backend with the weight-fp8 GEMMs; {type(ops).__name__} lacks {missing}")
+            tc_ = cfg.text
+            for name, K in (("hidden", tc_.hidden_size), ("q width", tc_.num_heads * tc_.head_dim), ("intermediate", tc_.intermediate_size)):
+                if K % 64:
+                    raise ValueError(f"prefill_fp8=True needs every GEMM K to be a multiple of 64 (one K-tile of the kernel): {name} is {K}")
         self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8)
         self._fp8_scratch = None           # llm_fp8: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
         self._fp8_scratch_owner = share._fp8_scratch_owner if share is not None else self      # whose scratch layer this engine uses
@@ -556,6 +575,10 @@ class SvlmEngine:
 
     # ------------------------------------------------------------------ LLM
     PREFILL_ROWS = 4096           # rows per pass of a long prefill (dense-frame prompts are tens of thousands of rows)
+    # prefill_fp8: a pass of more rows than this goes through the scratch layer (dequantisation + bf16 GEMMs).  Measured at the 7B widths
+    # (tools/gemm_wfp8_vs_bf16.py, profiles/gemm_wfp8_vs_bf16.json): the direct GEMMs of a layer take 0.79x the scratch
+    # path's time at M = 590 and 1.19x at M = 4096, where the conversion sits on a compute-bound loop and the dequantisation is amortised.
+    PREFILL_FP8_MAX_ROWS = 1024
 
     def _prefill(self, c: KVPool, idx_dev, vis, T: int, L_before: int, head: bool = True):
         """Rows L_before .. L_before+T-1 through all layers (their K/V rows go to the pool); `head`: last-row logits."""
@@ -576,7 +599,20 @@ class SvlmEngine:
         # decode steps of this chunk stream instead of rotating the pool rows again (kv_pool.py)
         lin = c.lin_args() if hasattr(c, "lin_args") else None
         o.rmsnorm(x, w.layers[0]["ln1"], tc.rms_eps, out=xn)
+        # the four GEMMs of a layer on the e4m3 codes: no dequantisation, no scratch layer
+        direct = self.prefill_fp8 and (self.PREFILL_FP8_MAX_ROWS is None or T <= self.PREFILL_FP8_MAX_ROWS)
         for li, lw in enumerate(w.layers):
+            if direct:
+                o.gemm_wfp8(xn, lw["qkv_w8"], lw["qkv_w_s"], bias=lw["qkv_b"], out=qkv)
+                o.prefill_attn(qkv[:, :qd], c.pool, li, c.slot_of_dev, self.rope_cs, attn, T, L, tc.num_heads, scale,
+                               k_new=qkv[:, qd:qd + kd], v_new=qkv[:, qd + kd:], lin=lin)
+                o.gemm_wfp8_norm(attn, lw["o_w8"], lw["o_w_s"], lw["ln2"], tc.rms_eps, x, xn, residual=x)
+                o.gemm_wfp8(xn, lw["gu_w8"], lw["gu_w_s"], out=hm, act=ACT_SWIGLU)          # H % 64 == 0 (checked at construction)
+                if li + 1 < n_layers:
+                    o.gemm_wfp8_norm(hm, lw["down_w8"], lw["down_w_s"], w.layers[li + 1]["ln1"], tc.rms_eps, x, xn, residual=x)
+                else:
+                    o.gemm_wfp8(hm, lw["down_w8"], lw["down_w_s"], residual=x, out=x)
+                continue
             if self.llm_fp8:
                 lw = self._dequant_layer(lw)
             o.gemm(xn, lw["qkv_w"], bias=lw["qkv_b"], out=qkv)

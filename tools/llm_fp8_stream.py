@@ -9,7 +9,12 @@ A stream run fills the KV window first, then times K chunks as bench.py does (ra
 and reports frames/s, ms per chunk, the chunk's decode steps (first replay start -> last replay end on the GPU timeline, beside the
 look-ahead ViT) and its LLM prefill (the per-layer dequantisation into the scratch layer included).  The kernel run times the five
 weight-streaming GEMVs in fp8 and bf16 at the model's shapes over 8 layers of distinct weights, cold (512 MiB written between
-replays), as bench.py's roofline pass does; bytes are each form's own weight bytes (+ scales, activations)."""
+replays), as bench.py's roofline pass does; bytes are each form's own weight bytes (+ scales, activations).
+
+`--prefill-fp8`: per model ONE child process builds the bf16 model, the scratch-layer fp8 model and the direct fp8 model
+(prefill_fp8=True: the prefill GEMMs read the e4m3 weights, csrc/gemm_wfp8.hip) and runs their streams in alternation, `--repeats` times
+each; the record (profiles/llm_fp8_prefill_<model>.json with --out) holds every pass, per form the median and the spread of the repeats
+of frames/s, ms per chunk and prefill ms per chunk, and direct - scratch / direct - bf16 prefill ms against that spread."""
 import argparse
 import json
 import os
@@ -25,7 +30,8 @@ SIZE, SINK, NEW = 448, 4, 20
 HBM_PEAK_GBS = 8000.0
 
 
-def stream_run(model_name, fp8, steps, warmup):
+def stream_run(model_name, fp8, steps, warmup, prefill_fp8=False, model=None):
+    """-> (record, model).  `model`: a model an earlier pass built (its engine's timing wrappers are taken off first)."""
     import torch
     import streaming_vlm_amd as S
     from streaming_vlm_amd import config as C
@@ -42,10 +48,13 @@ def stream_run(model_name, fp8, steps, warmup):
     first = fill + warmup
     n_chunks = first + steps + 1
     t_build = time.perf_counter()
-    model = S.StreamingQwen2VL(cfg, random_state_dict(cfg, 0, dev), dev, max_len=max_len, max_new_tokens=NEW, llm_fp8=fp8)
+    if model is None:
+        model = S.StreamingQwen2VL(cfg, random_state_dict(cfg, 0, dev), dev, max_len=max_len, max_new_tokens=NEW, llm_fp8=fp8,
+                                   **(dict(prefill_fp8=True) if prefill_fp8 else {}))
     torch.cuda.synchronize()
     build_s = time.perf_counter() - t_build
     eng = model._svlm_engine
+    plain = (eng._prefill, eng._decode_step)
     video = ResidentVideo(n_chunks + 1, SIZE, p["fps"], 0, dev)
     sec = {"prefill": [], "decode": []}
 
@@ -80,18 +89,19 @@ def stream_run(model_name, fp8, steps, warmup):
                           kv_policy="sink_window", sink=SINK, window=p["window"], do_sample=False, max_new_tokens=NEW, suppress_eos=True,
                           quiet=True, token_counts=counts, chunk_callback=on_chunk)
     torch.cuda.synchronize()
+    eng._prefill, eng._decode_step = plain
     timed = per_chunk[t["n0"]:t["n1"]]
     ms = lambda a, b: a.elapsed_time(b)
     elapsed = t["t1"] - t["t0"]
     frames = steps * video.frames_per_chunk
-    return {"run": "stream", "model": cfg.name, "llm_fp8": fp8, "config": f"{SIZE}x{SIZE} @{p['fps']:g}fps, sink {SINK} + window {p['window']}, "
+    return {"run": "stream", "model": cfg.name, "llm_fp8": fp8, "prefill_fp8": bool(prefill_fp8), "config": f"{SIZE}x{SIZE} @{p['fps']:g}fps, sink {SINK} + window {p['window']}, "
             f"{NEW} greedy tokens/chunk", "steps": steps, "warmup": warmup, "frames_per_sec": round(frames / elapsed, 3),
             "ms_per_chunk": round(1e3 * elapsed / steps, 3),
             "decode_ms_per_chunk": round(sum(ms(c[2], c[3]) for c in timed) / len(timed), 3),
             "decode_steps_per_chunk": timed[0][4] if timed else 0,
             "prefill_ms_per_chunk": round(sum(ms(c[0], c[1]) for c in timed) / len(timed), 3),
             "decode_weight_bytes": eng.w.decode_bytes(), "memory_allocated_GiB": round(torch.cuda.memory_allocated() / 2 ** 30, 2),
-            "build_seconds": round(build_s, 1)}
+            "build_seconds": round(build_s, 1)}, model
 
 
 def kernel_run(model_name, n_layers=8, reps=5):
@@ -159,21 +169,64 @@ def kernel_run(model_name, n_layers=8, reps=5):
     return {"run": "kernels", "model": model_name, "layers_per_replay": n_layers, "cold": "512 MiB written between replays", "kernels": res}
 
 
+def prefill_run(model_name, steps, warmup, repeats):
+    """bf16, scratch fp8 and direct fp8 streams of one model in ONE process, passes alternating; -> the record lines."""
+    import statistics
+    forms = {"bf16": dict(fp8=False), "fp8_scratch": dict(fp8=True), "fp8_direct": dict(fp8=True, prefill_fp8=True)}
+    models, passes = {}, {k: [] for k in forms}
+    for r in range(repeats):
+        for name, kw in forms.items():
+            rec, models[name] = stream_run(model_name, kw["fp8"], steps, warmup, kw.get("prefill_fp8", False), models.get(name))
+            rec.update(run="stream", form=name, repeat=r)
+            passes[name].append(rec)
+    lines = [p for ps in passes.values() for p in ps]
+    summ = {"run": "prefill_summary", "model": model_name, "repeats": repeats}
+    for name, ps in passes.items():
+        for key in ("frames_per_sec", "ms_per_chunk", "prefill_ms_per_chunk", "decode_ms_per_chunk"):
+            v = [p[key] for p in ps]
+            summ[f"{name}.{key}"] = {"median": round(statistics.median(v), 3), "spread": round(max(v) - min(v), 3)}
+    pm = lambda n: summ[f"{n}.prefill_ms_per_chunk"]
+    summ["prefill_ms_direct_minus_scratch"] = round(pm("fp8_direct")["median"] - pm("fp8_scratch")["median"], 3)
+    summ["prefill_ms_direct_minus_bf16"] = round(pm("fp8_direct")["median"] - pm("bf16")["median"], 3)
+    summ["prefill_ms_repeat_spread"] = max(pm(n)["spread"] for n in forms)
+    return lines + [summ]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("models", nargs="*", default=["2b", "7b"])
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None, help="directory: one llm_fp8_<model>.json per model (all of its lines)")
+    ap.add_argument("--prefill-fp8", action="store_true", help="bf16, scratch fp8 and direct fp8 (prefill_fp8=True) streams in one process per model")
+    ap.add_argument("--repeats", type=int, default=3, help="--prefill-fp8: passes per form (their spread is the noise)")
     ap.add_argument("--child", nargs=2, metavar=("MODEL", "RUN"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         m, run = args.child
-        out = kernel_run(m) if run == "kernels" else stream_run(m, run == "fp8", args.steps, args.warmup)
+        if run == "prefill":
+            for line in prefill_run(m, args.steps, args.warmup, args.repeats):
+                print(json.dumps(line), flush=True)
+            return
+        out = kernel_run(m) if run == "kernels" else stream_run(m, run == "fp8", args.steps, args.warmup)[0]
         print(json.dumps(out), flush=True)
         return
     for m in args.models:
         lines = []
+        if args.prefill_fp8:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--repeats",
+                                str(args.repeats), "--child", m, "prefill"], capture_output=True, text=True)
+            if p.returncode != 0:
+                sys.stderr.write(p.stderr[-4000:])
+                raise SystemExit(f"{m} prefill: child exited with {p.returncode}")
+            lines = [json.loads(l) for l in p.stdout.strip().splitlines() if l.startswith("{")]
+            for line in lines:
+                print(json.dumps(line), flush=True)
+            if args.out:
+                os.makedirs(args.out, exist_ok=True)
+                with open(os.path.join(args.out, f"llm_fp8_prefill_{m}.json"), "w") as f:
+                    json.dump(lines, f, indent=1)
+            continue
         for run in ("bf16", "fp8", "kernels"):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--child", m, run],
                                capture_output=True, text=True)

@@ -13,12 +13,17 @@ single-stream step graph.
 kernels (csrc/decode_batch_fp8.hip); the bf16 group passes of the same weights run in the same process ("group_bf16"), so the fp8 group
 is read against the bf16 group and the solo fp8 stream of ONE run, never against a profile of another day.
 
+`--prefill-fp8` (implies --llm-fp8): the fp8 model is built with prefill_fp8=True -- its prefill GEMMs read the e4m3 weights themselves
+(csrc/gemm_wfp8.hip), no dequantisation into a scratch layer -- and the groups of the scratch-layer fp8 model ("group_fp8_scratch") run in
+the same process beside the bf16 groups, so direct fp8, scratch fp8 and bf16 groups are all of ONE run.
+
 Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- python tools/stream_group_bench.py --kernels-only`
 (a run of its own, no counters) and pass the stats CSV with --kernel-stats to have the decb_* / single-row averages folded in.
 
     python tools/stream_group_bench.py --out profiles/stream_group_2b.json
     python tools/stream_group_bench.py --llm-fp8                                      (writes profiles/stream_group_fp8_2b.json)
     python tools/stream_group_bench.py --llm-fp8 --model 7b --fps 2 --window 4096     (writes profiles/stream_group_fp8_7b.json)
+    python tools/stream_group_bench.py --prefill-fp8 [--model 7b --fps 2 --window 4096]  (writes profiles/stream_group_prefill_fp8_<model>.json)
 """
 import argparse
 import csv
@@ -89,14 +94,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="single-stream passes (noise estimate)")
     ap.add_argument("--max-lanes", type=int, default=4)
     ap.add_argument("--llm-fp8", action="store_true", help="e4m3 language-model weights: fp8 solo + fp8 groups, and the bf16 groups of the same run")
+    ap.add_argument("--prefill-fp8", action="store_true", help="--llm-fp8 with the prefill on the e4m3 weights (prefill_fp8=True); the scratch-layer "
+                                                               "fp8 groups and the bf16 groups run in the same process")
     ap.add_argument("--kernels-only", action="store_true", help="one short pass per B and nothing else (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 kernel_stats CSV of a --kernels-only run")
     ap.add_argument("--fold", default=None, help="with --kernel-stats: add the kernel averages to this earlier record of the same workload "
                                                  "and write it to --out; no GPU work")
     ap.add_argument("--out", default=None, help="record file; --llm-fp8 timed runs default to profiles/stream_group_fp8_<model>.json")
     args = ap.parse_args()
+    args.llm_fp8 = args.llm_fp8 or args.prefill_fp8
     if args.llm_fp8 and not args.kernels_only and not args.fold and args.out is None:
-        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"stream_group_fp8_{args.model}.json")
+        stem = "stream_group_prefill_fp8" if args.prefill_fp8 else "stream_group_fp8"
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"{stem}_{args.model}.json")
 
     cfg = {"2b": C.qwen2_vl_2b, "7b": C.qwen2_vl_7b, "tiny": C.tiny}[args.model]()
     if args.fold:
@@ -115,7 +124,8 @@ def main():
     steps = 6 if args.kernels_only else args.steps
     n_chunks = fill + steps
     sd = random_state_dict(cfg, 0, dev)
-    model = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens, llm_fp8=args.llm_fp8)
+    model = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens, llm_fp8=args.llm_fp8,
+                               **(dict(prefill_fp8=True) if args.prefill_fp8 else {}))
     eng = model._svlm_engine
     base = "Qwen2"
     torch.set_num_threads(min(torch.get_num_threads(), 8))
@@ -190,6 +200,7 @@ def main():
 
     groups = out["group"] = group_passes(model)
     out["llm_fp8"] = bool(args.llm_fp8)
+    out["prefill_fp8"] = bool(args.prefill_fp8)
     out["decode_weight_bytes"] = eng.w.decode_bytes()
     if "solo" in out:
         ref = out["solo"]["frames_per_sec_median"]
@@ -203,6 +214,14 @@ def main():
         for B, rec in groups.items():
             rec["decode_step_vs_bf16_group"] = rec["decode_us_per_step"] / gb[B]["decode_us_per_step"]
             rec["frames_per_sec_vs_bf16_group"] = rec["frames_per_sec"] / gb[B]["frames_per_sec"]
+        del bf
+        if args.prefill_fp8:
+            # ... and the groups of the scratch-layer fp8 model (dequantisation + bf16 GEMMs per lane prefill), same weights, same run
+            sc = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens, llm_fp8=True)
+            gs = out["group_fp8_scratch"] = group_passes(sc)
+            for B, rec in groups.items():
+                rec["frames_per_sec_vs_scratch_group"] = rec["frames_per_sec"] / gs[B]["frames_per_sec"]
+            del sc
         best = lambda g: max(g, key=lambda B: g[B]["frames_per_sec"])
         out["best"] = dict(fp8_lanes=int(best(groups)), fp8_frames_per_sec=groups[best(groups)]["frames_per_sec"],
                            bf16_lanes=int(best(gb)), bf16_frames_per_sec=gb[best(gb)]["frames_per_sec"])
