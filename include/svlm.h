@@ -398,6 +398,41 @@ int svlm_decb_gemv_fp8(const void* lanes, int B, const void* x, int ldx, const v
 int svlm_decb_lm_head_fp8(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W8, int ldw,
                           const float* w_scale, float* logits, int ldl, const int* suppress, void* ws, int V, int K, void* stream);
 
+/* ---- stream groups: per-lane sampling (stream_group.py, StreamGroup(sampling=True)).  The reference's default token choice
+ * (do_sample=True at inference.py:446 with HF's warpers) for the lanes of a group: every lane has its own temperature / top-k / top-p and
+ * its own Philox seed, in a table of B svlm_lane_sample records parallel to the lane table (record b belongs to lane b).  `mode` is chosen
+ * by the host with the rule of svlm_penalty_sample: top_k == 1 greedy; top_k == 0 && top_p >= 1 Gumbel; top_k == 0 || top_k >= 2048
+ * nucleus; anything else filtered.  inv_temp is fp32(1) / fp32(temperature), the value the single-row entries compute on the host.  The
+ * counter of a draw stays (token index state[1] + 1, vocabulary index), so per lane every token is BITWISE the one the single-row entries
+ * (svlm_dec_lm_head[_sample][_fp8] + svlm_argmax_finish / svlm_penalty_sample) choose for the lane alone. */
+#define SVLM_SAMPLE_GREEDY 0   /* argmax of the processed scores (rng unused) */
+#define SVLM_SAMPLE_GUMBEL 1   /* plain temperature: Gumbel-max inside the lm_head candidates */
+#define SVLM_SAMPLE_FILTERED 2 /* 1 < top_k < 2048 (with or without top_p): select / sort / cut / inverse-CDF draw */
+#define SVLM_SAMPLE_NUCLEUS 3  /* top_p alone or a wider k: threshold form + Gumbel-max over the survivors */
+typedef struct svlm_lane_sample {
+  const unsigned* rng;  /* {seed lo, seed hi} of the lane's generate() call in device memory; NULL only for a greedy lane */
+  float inv_temp;
+  int top_k;
+  float top_p;
+  int mode;             /* SVLM_SAMPLE_* */
+} svlm_lane_sample;     /* 24 bytes */
+/* svlm_decb_lm_head / svlm_decb_lm_head_fp8 with one addition: a live lane in Gumbel mode gets score * inv_temp + Gumbel noise as its
+ * candidate score (svlm_dec_lm_head_sample); lanes in the other modes get the plain argmax candidates.  Every live lane's fp32 logits
+ * row is written as before; same weight streaming (each weight read and converted once for all lanes), same workspace layout.
+ * replaces: generate/streaming_generate_qwen.py:75,95-97 (logits processors, softmax + torch.multinomial) on the decode steps of a group. */
+int svlm_decb_lm_head_sample(const void* lanes, const void* samples, int B, const void* x, int ldx, const void* ln_w, float eps,
+                             const void* W, int ldw, float* logits, int ldl, const int* suppress, void* ws, int V, int K, void* stream);
+int svlm_decb_lm_head_sample_fp8(const void* lanes, const void* samples, int B, const void* x, int ldx, const void* ln_w, float eps,
+                                 const void* W8, int ldw, const float* w_scale, float* logits, int ldl, const int* suppress, void* ws, int V,
+                                 int K, void* stream);
+/* The token choice of every lane in ONE launch, one workgroup per lane: greedy and Gumbel lanes take the winner over their candidates
+ * (svlm_argmax_finish), filtered and nucleus lanes draw from their own logits row logits + b * ldl (svlm_penalty_sample; penalty, seen
+ * and n_suppress from the lane record, the rest from the sampling record), then the same device-side token feedback.  A lane that is
+ * not live is skipped.  When V is a multiple of 4 the rows must be 16-B aligned (ldl a multiple of 4).
+ * replaces: generate/streaming_generate_qwen.py:75,92-97,99,104. */
+int svlm_decb_sample_finish(const void* lanes, const void* samples, int B, const float* logits, int ldl, const int* suppress,
+                            const void* ws, int V, int advance_kv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,17 @@ struct svlm_lane {                 // mirror of include/svlm.h
 };
 static_assert(sizeof(svlm_lane) == 72, "svlm_lane layout (include/svlm.h)");
 
+// The sampling record of a lane, in a table of its own parallel to the lane table (svlm_decb_lm_head_sample / svlm_decb_sample_finish).
+struct svlm_lane_sample {          // mirror of include/svlm.h
+  const unsigned* rng;             // {seed lo, seed hi} of the lane's current generate() call, or null (greedy)
+  float inv_temp;                  // fp32(1) / fp32(temperature), divided on the host as the single-row entries do
+  int top_k;
+  float top_p;
+  int mode;                        // SVLM_SAMPLE_*
+};
+static_assert(sizeof(svlm_lane_sample) == 24, "svlm_lane_sample layout (include/svlm.h)");
+enum { SVLM_SAMPLE_GREEDY = 0, SVLM_SAMPLE_GUMBEL = 1, SVLM_SAMPLE_FILTERED = 2, SVLM_SAMPLE_NUCLEUS = 3 };
+
 __device__ __forceinline__ bool lane_live(const svlm_lane& L) { return L.state[1] + 1 < L.limit; }
 
 // Prologue of the fused kernels: the live lanes' x rows are requested first, then the head of the weight stream, then the rows are

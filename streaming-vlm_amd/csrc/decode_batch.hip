@@ -8,6 +8,10 @@
 //   svlm_decb_gate_up        batched svlm_dec_gate_up
 //   svlm_decb_lm_head        batched svlm_dec_lm_head (greedy: penalty, suppression, argmax candidates per lane)
 //   svlm_decb_argmax_finish  batched svlm_argmax_finish, one workgroup per lane
+//   svlm_decb_lm_head_sample svlm_decb_lm_head whose candidates carry the Gumbel noise of svlm_dec_lm_head_sample for the lanes that
+//                            draw with a plain temperature (per-lane sampling records, struct svlm_lane_sample)
+//   svlm_decb_sample_finish  one workgroup per lane: svlm_argmax_finish over the candidates (greedy, Gumbel) or the top-k / top-p
+//                            draw of svlm_penalty_sample on the lane's own logits row (dec_sample.h)
 //
 // Each wave loads its weight rows once (the same 16-B non-temporal loads and PRE run-ahead as decode_fused.hip) and multiplies them
 // with the NB activation rows of the group.  The fused kernels stage the NB normalised rows in LDS; svlm_decb_gemv reads its NB
@@ -26,6 +30,7 @@
 #include "dec_xrow.h"
 #include "dec_stream.h"
 #include "dec_lanes.h"            // svlm_lane, lane_live, load_rows, stage_rows: shared with decode_batch_fp8.hip
+#include "dec_sample.h"
 
 // acc[b][r] += W[row r] . xs[b] over the PRE K-steps held in `pre`; per (b, r) the same FMA sequence as fma_batch (decode_fused.hip)
 template <int NB, int NR, int PRE>
@@ -166,11 +171,13 @@ __global__ __launch_bounds__(256) void decb_gate_up_kernel(const svlm_lane* __re
 
 // ---------------------------------------------------------------- lm_head + penalty + argmax candidates
 #define DECB_LM_ROWS 2            // = LM_ROWS of decode_fused.hip: the candidates are per workgroup of 4 x LM_ROWS vocabulary rows
-template <int NB, int PRE, int XC>
-__global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
-                                                           const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
-                                                           float* __restrict__ logits, int ldl, const int* __restrict__ suppress,
-                                                           float* __restrict__ ws, long long ws_stride, int V, int K) {
+// SMP: a live lane whose sampling record says Gumbel gets score * inv_temp + noise(seed, token index, vocabulary index) as its candidate
+// score, the expression of dec_lm_head_kernel (decode_fused.hip); the logits row and the other lanes' candidates do not change.
+template <int NB, int PRE, int XC, bool SMP>
+__device__ __forceinline__ void decb_lm_head_body(const svlm_lane* __restrict__ lanes, const svlm_lane_sample* __restrict__ samples,
+                                                  const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ ln_w, float eps,
+                                                  const bf16_t* __restrict__ W, int ldw, float* __restrict__ logits, int ldl,
+                                                  const int* __restrict__ suppress, float* __restrict__ ws, long long ws_stride, int V, int K) {
   constexpr int ROWS = DECB_LM_ROWS;
   bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -197,6 +204,11 @@ __global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __re
     for (int b = 0; b < NB; ++b) {
       if (!live[b]) continue;
       const svlm_lane& L = lanes[b];
+      const unsigned* rng = nullptr;
+      float inv_temp = 1.0f;
+      if constexpr (SMP) {
+        if (samples[b].mode == SVLM_SAMPLE_GUMBEL) { rng = samples[b].rng; inv_temp = samples[b].inv_temp; }
+      }
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) {
         const int n = n0 + r;
@@ -206,6 +218,9 @@ __global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __re
         if (L.seen && L.seen[n]) v = v < 0.f ? v * L.penalty : v / L.penalty;
         for (int s = 0; s < L.n_suppress; ++s)
           if (suppress[s] == n) v = -INFINITY;
+        if constexpr (SMP) {
+          if (rng) v = v * inv_temp + svlm_gumbel_noise(rng, (unsigned)(L.state[1] + 1), (unsigned)n);
+        }
         if (v > best[b] || (v == best[b] && n < bi[b])) { best[b] = v; bi[b] = n; }
       }
     }
@@ -230,12 +245,54 @@ __global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __re
   }
 }
 
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                           const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
+                                                           float* __restrict__ logits, int ldl, const int* __restrict__ suppress,
+                                                           float* __restrict__ ws, long long ws_stride, int V, int K) {
+  decb_lm_head_body<NB, PRE, XC, false>(lanes, nullptr, x, ldx, ln_w, eps, W, ldw, logits, ldl, suppress, ws, ws_stride, V, K);
+}
+
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_lm_head_sample_kernel(const svlm_lane* __restrict__ lanes,
+                                                                  const svlm_lane_sample* __restrict__ samples, const bf16_t* __restrict__ x,
+                                                                  int ldx, const bf16_t* __restrict__ ln_w, float eps,
+                                                                  const bf16_t* __restrict__ W, int ldw, float* __restrict__ logits, int ldl,
+                                                                  const int* __restrict__ suppress, float* __restrict__ ws,
+                                                                  long long ws_stride, int V, int K) {
+  decb_lm_head_body<NB, PRE, XC, true>(lanes, samples, x, ldx, ln_w, eps, W, ldw, logits, ldl, suppress, ws, ws_stride, V, K);
+}
+
 __global__ __launch_bounds__(1024) void decb_argmax_finish_kernel(const svlm_lane* __restrict__ lanes, const float* __restrict__ ws,
                                                                   long long ws_stride, int n_parts, int advance_kv) {
   const svlm_lane& L = lanes[blockIdx.x];
   if (!lane_live(L)) return;
   const float* pv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ws) + (size_t)blockIdx.x * ws_stride);
   argmax_finish_body(pv, reinterpret_cast<const int*>(pv + n_parts), n_parts, L.seen, L.tok_buf, L.state, advance_kv);
+}
+
+// One workgroup per lane, ONE kernel that branches on the lane's mode (workgroup-uniform): a batch is at most 4 workgroups, so the
+// 35 KB of static LDS the filtered body brings to every workgroup costs no occupancy, and the lanes' draws run side by side in one
+// launch whatever mix of modes the batch holds.
+__global__ __launch_bounds__(SF_THREADS) void decb_sample_finish_kernel(const svlm_lane* __restrict__ lanes,
+                                                                        const svlm_lane_sample* __restrict__ samples,
+                                                                        const float* __restrict__ logits, int ldl,
+                                                                        const int* __restrict__ suppress, const float* __restrict__ ws,
+                                                                        long long ws_stride, int n_parts, int V, int advance_kv) {
+  const svlm_lane& L = lanes[blockIdx.x];
+  if (!lane_live(L)) return;
+  const svlm_lane_sample& S = samples[blockIdx.x];
+  const float* row = logits + (size_t)blockIdx.x * ldl;
+  if (S.mode == SVLM_SAMPLE_FILTERED) {
+    sample_filtered_body(row, V, L.seen, L.penalty, suppress, L.n_suppress, S.inv_temp, S.top_k, S.top_p, S.rng, L.seen, L.tok_buf, L.state,
+                         advance_kv);
+  } else if (S.mode == SVLM_SAMPLE_NUCLEUS) {
+    sample_nucleus_body(row, V, L.seen, L.penalty, suppress, L.n_suppress, S.inv_temp, S.top_k, S.top_p, S.rng, L.seen, L.tok_buf, L.state,
+                        advance_kv);
+  } else {
+    const float* pv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ws) + (size_t)blockIdx.x * ws_stride);
+    argmax_finish_body(pv, reinterpret_cast<const int*>(pv + n_parts), n_parts, L.seen, L.tok_buf, L.state, advance_kv);
+  }
 }
 
 // ---------------------------------------------------------------- residual GEMVs (o_proj, down_proj)
@@ -494,4 +551,31 @@ extern "C" int svlm_decb_argmax_finish(const void* lanes, int B, const void* ws,
   decb_argmax_finish_kernel<<<B, 1024, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const float*)ws, svlm_decb_lm_head_ws_stride(V), nb,
                                                                  advance_kv);
   return svlm_check_launch("svlm_decb_argmax_finish");
+}
+
+extern "C" int svlm_decb_lm_head_sample(const void* lanes, const void* samples, int B, const void* x, int ldx, const void* ln_w, float eps,
+                                        const void* W, int ldw, float* logits, int ldl, const int* suppress, void* ws, int V, int K,
+                                        void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && samples != nullptr && decb_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0 && V > 0 && ldl >= V,
+                 "svlm_decb_lm_head_sample: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d or no lane / sample table", B, V, K, ldx, ldw, ldl);
+  SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head_sample: null logits / workspace");
+  const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
+  DECB_DISPATCH(decb_lm_head_sample_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const svlm_lane_sample*)samples, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, logits,
+      ldl, suppress, (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K));
+  return svlm_check_launch("svlm_decb_lm_head_sample");
+}
+
+extern "C" int svlm_decb_sample_finish(const void* lanes, const void* samples, int B, const float* logits, int ldl, const int* suppress,
+                                       const void* ws, int V, int advance_kv, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && samples != nullptr && B >= 1 && B <= 4 && V > 0 && ws != nullptr && logits != nullptr && ldl >= V,
+                 "svlm_decb_sample_finish: bad B=%d V=%d ldl=%d or a null table / logits / workspace", B, V, ldl);
+  // the row scan takes 16-B loads when V is a multiple of 4: every lane's row must then start on a 16-B boundary
+  SVLM_CHECK_ARG(V % 4 != 0 || (ldl % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0),
+                 "svlm_decb_sample_finish: logits rows of V=%d need a 16-B aligned base and ldl=%d a multiple of 4", V, ldl);
+  const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
+  decb_sample_finish_kernel<<<B, SF_THREADS, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const svlm_lane_sample*)samples, logits, ldl,
+                                                                       suppress, (const float*)ws, svlm_decb_lm_head_ws_stride(V), nb, V,
+                                                                       advance_kv);
+  return svlm_check_launch("svlm_decb_sample_finish");
 }

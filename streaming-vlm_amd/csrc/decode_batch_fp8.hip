@@ -7,6 +7,8 @@
 //   svlm_decb_gemv_fp8     svlm_gemv_fp8          o_proj / down_proj + residual, every dispatch branch of the single-row entry
 //   svlm_decb_lm_head_fp8  svlm_dec_lm_head_fp8   greedy: penalty, suppression, argmax candidates per lane (svlm_decb_argmax_finish and
 //                                                 svlm_decb_lm_head_ws_stride of decode_batch.hip serve unchanged)
+//   svlm_decb_lm_head_sample_fp8  svlm_dec_lm_head_sample_fp8  the same with Gumbel noise in the candidates of the lanes whose sampling
+//                                                 record says so (completed by svlm_decb_sample_finish of decode_batch.hip)
 //
 // A wave loads its weight rows once (16-B non-temporal loads straight to VGPRs, every load of a batch issued before its first FMA),
 // converts each 16-code vector to fp32 ONCE and multiplies the converted values with the NB activation rows of the group: the batch
@@ -168,12 +170,14 @@ __global__ __launch_bounds__(256) void decb_gate_up_fp8_kernel(const svlm_lane* 
 
 // ---------------------------------------------------------------- lm_head + penalty + argmax candidates
 #define DECB_LM8_ROWS 2           // = LM8_ROWS of decode_fp8.hip = DECB_LM_ROWS of decode_batch.hip: one candidate per 8 vocabulary rows
-template <int NB, int PRE, int XC>
-__global__ __launch_bounds__(256) void decb_lm_head_fp8_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
-                                                               const bf16_t* __restrict__ ln_w, float eps, const fp8_t* __restrict__ W,
-                                                               int ldw, const float* __restrict__ w_scale, float* __restrict__ logits,
-                                                               int ldl, const int* __restrict__ suppress, float* __restrict__ ws,
-                                                               long long ws_stride, int V, int K) {
+// SMP: as decb_lm_head_body (decode_batch.hip) -- a live lane in Gumbel mode gets score * inv_temp + noise as its candidate score, the
+// expression of dec_lm_head_fp8_kernel (decode_fp8.hip).
+template <int NB, int PRE, int XC, bool SMP>
+__device__ __forceinline__ void decb_lm_head_fp8_body(const svlm_lane* __restrict__ lanes, const svlm_lane_sample* __restrict__ samples,
+                                                      const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ ln_w, float eps,
+                                                      const fp8_t* __restrict__ W, int ldw, const float* __restrict__ w_scale,
+                                                      float* __restrict__ logits, int ldl, const int* __restrict__ suppress,
+                                                      float* __restrict__ ws, long long ws_stride, int V, int K) {
   constexpr int ROWS = DECB_LM8_ROWS;
   bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -203,6 +207,11 @@ __global__ __launch_bounds__(256) void decb_lm_head_fp8_kernel(const svlm_lane* 
     for (int b = 0; b < NB; ++b) {
       if (!live[b]) continue;
       const svlm_lane& L = lanes[b];
+      const unsigned* rng = nullptr;
+      float inv_temp = 1.0f;
+      if constexpr (SMP) {
+        if (samples[b].mode == SVLM_SAMPLE_GUMBEL) { rng = samples[b].rng; inv_temp = samples[b].inv_temp; }
+      }
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) {
         const int n = n0 + r;
@@ -212,6 +221,9 @@ __global__ __launch_bounds__(256) void decb_lm_head_fp8_kernel(const svlm_lane* 
         if (L.seen && L.seen[n]) v = v < 0.f ? v * L.penalty : v / L.penalty;
         for (int s = 0; s < L.n_suppress; ++s)
           if (suppress[s] == n) v = -INFINITY;
+        if constexpr (SMP) {
+          if (rng) v = v * inv_temp + svlm_gumbel_noise(rng, (unsigned)(L.state[1] + 1), (unsigned)n);
+        }
         if (v > best[b] || (v == best[b] && n < bi[b])) { best[b] = v; bi[b] = n; }
       }
     }
@@ -234,6 +246,26 @@ __global__ __launch_bounds__(256) void decb_lm_head_fp8_kernel(const svlm_lane* 
     pv[blockIdx.x] = bb;
     pi[blockIdx.x] = ii;
   }
+}
+
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_lm_head_fp8_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
+                                                               const bf16_t* __restrict__ ln_w, float eps, const fp8_t* __restrict__ W,
+                                                               int ldw, const float* __restrict__ w_scale, float* __restrict__ logits,
+                                                               int ldl, const int* __restrict__ suppress, float* __restrict__ ws,
+                                                               long long ws_stride, int V, int K) {
+  decb_lm_head_fp8_body<NB, PRE, XC, false>(lanes, nullptr, x, ldx, ln_w, eps, W, ldw, w_scale, logits, ldl, suppress, ws, ws_stride, V, K);
+}
+
+template <int NB, int PRE, int XC>
+__global__ __launch_bounds__(256) void decb_lm_head_sample_fp8_kernel(const svlm_lane* __restrict__ lanes,
+                                                                      const svlm_lane_sample* __restrict__ samples,
+                                                                      const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ ln_w,
+                                                                      float eps, const fp8_t* __restrict__ W, int ldw,
+                                                                      const float* __restrict__ w_scale, float* __restrict__ logits, int ldl,
+                                                                      const int* __restrict__ suppress, float* __restrict__ ws,
+                                                                      long long ws_stride, int V, int K) {
+  decb_lm_head_fp8_body<NB, PRE, XC, true>(lanes, samples, x, ldx, ln_w, eps, W, ldw, w_scale, logits, ldl, suppress, ws, ws_stride, V, K);
 }
 
 // ---------------------------------------------------------------- residual GEMVs (o_proj, down_proj)
@@ -416,4 +448,17 @@ extern "C" int svlm_decb_lm_head_fp8(const void* lanes, int B, const void* x, in
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale, logits, ldl, suppress,
       (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K));
   return svlm_check_launch("svlm_decb_lm_head_fp8");
+}
+
+extern "C" int svlm_decb_lm_head_sample_fp8(const void* lanes, const void* samples, int B, const void* x, int ldx, const void* ln_w, float eps,
+                                            const void* W8, int ldw, const float* w_scale, float* logits, int ldl, const int* suppress,
+                                            void* ws, int V, int K, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && samples != nullptr && decb8_ok(B, K, ldx, ldw) && w_scale != nullptr && V > 0 && ldl >= V,
+                 "svlm_decb_lm_head_sample_fp8: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d or no lane / sample table / scales", B, V, K, ldx, ldw, ldl);
+  SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head_sample_fp8: null logits / workspace");
+  const int nb = (V + 4 * DECB_LM8_ROWS - 1) / (4 * DECB_LM8_ROWS);
+  DECB8_DISPATCH(decb_lm_head_sample_fp8_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const svlm_lane_sample*)samples, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale,
+      logits, ldl, suppress, (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K));
+  return svlm_check_launch("svlm_decb_lm_head_sample_fp8");
 }

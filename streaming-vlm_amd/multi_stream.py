@@ -73,21 +73,25 @@ class StreamGroupError(RuntimeError):
         self.index, self.results = index, results
 
 
-def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Optional[int] = None, group=None, **common_kw) -> List:
+def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Optional[int] = None, group=None, sampling: bool = False,
+                              **common_kw) -> List:
     """Run `len(streams)` streams on ONE GPU through a stream group: each entry of `streams` holds the per-stream keyword arguments of
     `streaming_inference` (video_path, query, previous_text, duration, ...), `common_kw` the shared ones.  Every stream runs the
     unchanged `streaming_inference` loop in its own host thread against its lane's model object; the lanes' generate() calls meet in
     the group, which runs one batch when every lane that still has a stream has a request pending.  `n_lanes` defaults to min(3, streams): the measured
     aggregate throughput stops growing there.  More streams than lanes: they are
     queued, and a lane that finishes a stream takes the next one; a lane with nothing left detaches and the rest carry on.
-    Greedy decoding only (pass do_sample=False, or top_k=1); strict-causal (no look-ahead ViT).  Returns the per-stream response
+    Token choice: greedy only by default (pass do_sample=False, or top_k=1); with `sampling=True` the group is built as
+    `StreamGroup(..., sampling=True)` and every stream may carry its own `do_sample / temperature / top_k / top_p / generator` -- each
+    lane then produces the tokens of that stream run alone on a fresh model with the same generator seed (an existing `group` passed in
+    keeps the setting it was built with).  Strict-causal (no look-ahead ViT).  Returns the per-stream response
     lists in the order of `streams`; if a stream raised, the others still run to their end and a `StreamGroupError` naming the first
     failed stream's index is raised afterwards."""
     import threading
     from .driver import streaming_inference
     from .stream_group import DEFAULT_LANES, StreamGroup
     if group is None:
-        group = StreamGroup(model._svlm_engine, min(DEFAULT_LANES, len(streams)) if n_lanes is None else n_lanes)
+        group = StreamGroup(model._svlm_engine, min(DEFAULT_LANES, len(streams)) if n_lanes is None else n_lanes, sampling=sampling)
     results: List = [None] * len(streams)
     errors = {}
     lock = threading.Lock()

@@ -673,6 +673,49 @@ class HipOps:
         tail[3:4].view(np.float32)[0] = float(penalty)
         return rec
 
+    # per-lane sampling records (svlm_lane_sample, include/svlm.h): a table parallel to the lane table
+    SAMPLE_WORDS = 3        # int64 words of one svlm_lane_sample record
+    SAMPLE_GREEDY, SAMPLE_GUMBEL, SAMPLE_FILTERED, SAMPLE_NUCLEUS = 0, 1, 2, 3
+
+    @staticmethod
+    def sample_mode(top_k, top_p):
+        """The kernel a (top_k, top_p) setting takes: the dispatch rule of svlm_penalty_sample (csrc/sampling.hip)."""
+        top_k, top_p = int(top_k), float(top_p)
+        if top_k == 1:
+            return HipOps.SAMPLE_GREEDY
+        if top_k == 0 and top_p >= 1.0:
+            return HipOps.SAMPLE_GUMBEL
+        if top_k == 0 or top_k >= 2048:
+            return HipOps.SAMPLE_NUCLEUS
+        return HipOps.SAMPLE_FILTERED
+
+    @staticmethod
+    def lane_sample_record(rng=None, temperature=1.0, top_k=1, top_p=1.0):
+        """One svlm_lane_sample record as int64[SAMPLE_WORDS] on the host; the defaults are a greedy lane.  inv_temp is divided here
+        in fp32, as the single-row entries divide it on the host: the kernels multiply by the same bits."""
+        import numpy as np
+        top_k, top_p = int(top_k), float(top_p)
+        if not (float(temperature) > 0 and top_k >= 0 and 0.0 < top_p <= 1.0):
+            raise _lib.SvlmError(f"lane_sample_record: bad temperature={temperature} top_k={top_k} top_p={top_p}")
+        mode = HipOps.sample_mode(top_k, top_p)
+        if mode != HipOps.SAMPLE_GREEDY:
+            if rng is None:
+                raise _lib.SvlmError("lane_sample_record: a lane that draws needs its seed (rng, uint32[2] in device memory)")
+            _req(rng, torch.int32, "lane_sample_record.rng", 1)
+            assert rng.numel() >= 2
+        rec = np.zeros(HipOps.SAMPLE_WORDS, dtype=np.int64)
+        rec[0] = _ptr(rng) if mode != HipOps.SAMPLE_GREEDY else 0
+        rec[1:2].view(np.float32)[0] = np.float32(1.0) / np.float32(temperature)
+        rec[1:2].view(np.int32)[1] = top_k
+        rec[2:3].view(np.float32)[0] = np.float32(top_p)
+        rec[2:3].view(np.int32)[1] = mode
+        return rec
+
+    def _samples(self, samples, B, what):
+        _req(samples, torch.int64, what + ".samples", 2)
+        if not (samples.shape[0] >= B and samples.shape[1] == self.SAMPLE_WORDS and samples.is_contiguous()):
+            raise _lib.SvlmError(f"{what}: sample table {tuple(samples.shape)} for B={B} (records of {self.SAMPLE_WORDS} words)")
+
     def _lanes(self, lanes, B, what):
         _req(lanes, torch.int64, what + ".lanes", 2)
         if not (1 <= B <= 4 and lanes.shape[0] >= B and lanes.shape[1] == self.LANE_WORDS and lanes.is_contiguous()):
@@ -734,6 +777,28 @@ class HipOps:
         assert ws.is_contiguous() and ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
         self._check(self.lib.svlm_decb_argmax_finish(_ptr(lanes), B, _ptr(ws), V, int(advance_kv), _stream()), "svlm_decb_argmax_finish")
 
+    def decb_lm_head_sample(self, lanes, samples, B, x, ln_w, eps, W, logits, suppress, ws):
+        """decb_lm_head with Gumbel noise in the candidates of the lanes whose sampling record says so; completed by decb_sample_finish."""
+        self._lanes(lanes, B, "decb_lm_head_sample"); self._samples(samples, B, "decb_lm_head_sample")
+        _req(ln_w, BF16, "decb_lm_head_sample.ln_w", 1); _req(W, BF16, "decb_lm_head_sample.W", 2)
+        _req(suppress, torch.int32, "decb_lm_head_sample.suppress", 1); _req(ws, torch.float32, "decb_lm_head_sample.ws", 2)
+        V, K = W.shape
+        assert ln_w.numel() == K and suppress.numel() >= 8 and ws.is_contiguous()
+        assert ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        ldx, ldl = self._rows(x, B, K, "decb_lm_head_sample.x"), self._rows(logits, B, V, "decb_lm_head_sample.logits", torch.float32)
+        self._check(self.lib.svlm_decb_lm_head_sample(_ptr(lanes), _ptr(samples), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0),
+                                                _ptr(logits), ldl, _ptr(suppress), _ptr(ws), V, K, _stream()), "svlm_decb_lm_head_sample")
+
+    def decb_sample_finish(self, lanes, samples, B, logits, suppress, ws, V, advance_kv):
+        """Every lane's token choice in one launch (one workgroup per lane): the winner over its candidates (greedy, Gumbel) or the top-k /
+        top-p draw on its logits row, then the token feedback."""
+        self._lanes(lanes, B, "decb_sample_finish"); self._samples(samples, B, "decb_sample_finish")
+        _req(suppress, torch.int32, "decb_sample_finish.suppress", 1); _req(ws, torch.float32, "decb_sample_finish.ws", 2)
+        assert suppress.numel() >= 8 and ws.is_contiguous() and ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        ldl = self._rows(logits, B, V, "decb_sample_finish.logits", torch.float32)
+        self._check(self.lib.svlm_decb_sample_finish(_ptr(lanes), _ptr(samples), B, _ptr(logits), ldl, _ptr(suppress), _ptr(ws), int(V),
+                                               int(advance_kv), _stream()), "svlm_decb_sample_finish")
+
     # the same on e4m3 weights with per-row scales (csrc/decode_batch_fp8.hip): (W8, w_scale) where W stands; decb_embed,
     # decb_sampling_ws and decb_argmax_finish serve both
     def decb_qkv_fp8(self, lanes, B, x, ln_w, eps, W8, w_scale, bias, q_out, layer, qd, kd, D, n_layers):
@@ -770,6 +835,19 @@ class HipOps:
         ldx, ldl = self._rows(x, B, K, "decb_lm_head_fp8.x"), self._rows(logits, B, V, "decb_lm_head_fp8.logits", torch.float32)
         self._check(self.lib.svlm_decb_lm_head_fp8(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0), _ptr(w_scale),
                                              _ptr(logits), ldl, _ptr(suppress), _ptr(ws), V, K, _stream()), "svlm_decb_lm_head_fp8")
+
+    def decb_lm_head_sample_fp8(self, lanes, samples, B, x, ln_w, eps, W8, w_scale, logits, suppress, ws):
+        """decb_lm_head_sample on e4m3 rows: the same candidates in `ws`, completed by decb_sample_finish."""
+        self._lanes(lanes, B, "decb_lm_head_sample_fp8"); self._samples(samples, B, "decb_lm_head_sample_fp8")
+        _req(ln_w, BF16, "decb_lm_head_sample_fp8.ln_w", 1)
+        _req(suppress, torch.int32, "decb_lm_head_sample_fp8.suppress", 1); _req(ws, torch.float32, "decb_lm_head_sample_fp8.ws", 2)
+        V, K = self._req_fp8(W8, w_scale, "decb_lm_head_sample_fp8")
+        assert ln_w.numel() == K and suppress.numel() >= 8 and ws.is_contiguous()
+        assert ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        ldx, ldl = self._rows(x, B, K, "decb_lm_head_sample_fp8.x"), self._rows(logits, B, V, "decb_lm_head_sample_fp8.logits", torch.float32)
+        self._check(self.lib.svlm_decb_lm_head_sample_fp8(_ptr(lanes), _ptr(samples), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W8), W8.stride(0),
+                                                    _ptr(w_scale), _ptr(logits), ldl, _ptr(suppress), _ptr(ws), V, K, _stream()),
+              "svlm_decb_lm_head_sample_fp8")
 
     # ------------------------------------------------------------------ fp8 language-model weights (csrc/decode_fp8.hip)
     @staticmethod

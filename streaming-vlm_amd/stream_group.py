@@ -10,8 +10,19 @@ everything a stream owns: KV pool, positions, rope table, sampling state, evicti
 lane; per lane the tokens, cache length and logical order are EXACTLY those of the stream run alone (the batched kernels are bitwise
 the single-row ones per lane, and the decode attention is the unchanged single-stream kernel, launched once per lane).
 
+Token choice.  By default a group is greedy.  `StreamGroup(..., sampling=True)` batches the reference's default token choice as well:
+every lane's request carries its own `do_sample / temperature / top_k / top_p / generator`, and one batch may mix greedy, plain
+temperature, top-k (with or without top-p) and top-p alone.  `generate_begin` draws a lane's first token with the single-row kernels and
+sets the lane's Philox seed (`lane.rng_dev`) as it does for a stream alone; the group then writes one `svlm_lane_sample` record per lane
+(seed pointer, fp32 1/T, k, p and the kernel the setting takes) next to the lane record, and a step with any sampled lane ends in
+`decb_lm_head_sample[_fp8]` + `decb_sample_finish` (one workgroup per lane, all lanes in one launch) instead of `decb_lm_head[_fp8]` +
+`decb_argmax_finish`.  Per lane the draws are bitwise the single-row ones, so the tokens are those of the stream run alone on a fresh
+engine with the same generator seed (a seed mixes in how many sampled calls the lane's engine has made).
+
 Opt-in; nothing here is reached by the single-stream path.  Refused with a ValueError instead of silently falling back:
-`decode_tail=True` engines, an `llm_fp8=True` engine whose ops backend lacks the batched fp8 entry points, `do_sample=True` with anything but `top_k == 1`, `force_tokens`, `keep_logits`.
+`decode_tail=True` engines, an `llm_fp8=True` engine whose ops backend lacks the batched fp8 entry points (with `sampling=True` also the
+fp8 sampling head), `do_sample=True` with anything but `top_k == 1` unless the group was built with `sampling=True`, `force_tokens`,
+`keep_logits`.
 The look-ahead ViT (`next_vision`) is DECLINED: a group runs strict-causal, every chunk's vision tower runs inside its own
 `generate_begin`.
 """
@@ -38,16 +49,17 @@ DEFAULT_LANES = 3
 FP8_GROUP_OPS = ("decb_qkv_fp8", "decb_gate_up_fp8", "decb_gemv_fp8", "decb_lm_head_fp8")
 
 
-def check_request(req: dict) -> dict:
-    """Validate one lane's request (the keyword arguments of `SvlmEngine.generate`); returns it without the declined `next_vision`."""
+def check_request(req: dict, sampling: bool = False) -> dict:
+    """Validate one lane's request (the keyword arguments of `SvlmEngine.generate`); returns it without the declined `next_vision`.
+    `sampling`: the group batches sampled lanes (`StreamGroup(sampling=True)`), so every setting `generate_begin` accepts passes."""
     req = dict(req)
     req.pop("next_vision", None)
     if req.get("force_tokens") is not None:
         raise ValueError("stream group: force_tokens (teacher forcing) is a single-stream parity aid and is not supported")
     if req.get("keep_logits"):
         raise ValueError("stream group: keep_logits is not supported (the per-step logits of a lane stay on the device)")
-    if req.get("do_sample") and req.get("top_k") != 1:
-        raise ValueError("stream group: only greedy decoding is batched; do_sample=True needs top_k=1 "
+    if not sampling and req.get("do_sample") and req.get("top_k") != 1:
+        raise ValueError("stream group: only greedy decoding is batched unless the group was built with sampling=True; do_sample=True needs top_k=1 "
                          f"(got top_k={req.get('top_k')!r}, top_p={req.get('top_p')!r})")
     return req
 
@@ -148,7 +160,7 @@ class LaneModel:
 
 
 class StreamGroup:
-    def __init__(self, engine: SvlmEngine, n_lanes: int = 2):
+    def __init__(self, engine: SvlmEngine, n_lanes: int = 2, sampling: bool = False):
         if not 1 <= int(n_lanes) <= MAX_LANES:
             raise ValueError(f"n_lanes={n_lanes} outside [1, {MAX_LANES}]")
         if getattr(engine, "llm_fp8", False):
@@ -156,10 +168,14 @@ class StreamGroup:
             if missing:
                 raise ValueError(f"stream group: an llm_fp8=True engine needs an ops backend with the lane-batched fp8 entry points; "
                                  f"{type(getattr(engine, 'ops', None)).__name__} lacks {missing}")
+            if sampling and not hasattr(engine.ops, "decb_lm_head_sample_fp8"):
+                raise ValueError(f"stream group: sampling=True on an llm_fp8=True engine needs an ops backend with the lane-batched fp8 "
+                                 f"sampling head; {type(engine.ops).__name__} lacks decb_lm_head_sample_fp8")
         if getattr(engine, "decode_tail", False):
             raise ValueError("stream group: decode_tail=True engines are not supported (the persistent layer tail is single-row)")
         self.engine = engine
         self.n_lanes = int(n_lanes)
+        self.sampling = bool(sampling)
         tc, dev, o = engine.cfg.text, engine.device, engine.ops
         self.lanes: List[SvlmEngine] = [engine] + [
             SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
@@ -189,6 +205,13 @@ class StreamGroup:
         self._table_host = torch.zeros((2 * B, W), dtype=torch.int64)
         if dev.type == "cuda":
             self._table_host = self._table_host.pin_memory()
+        # the sampling table (svlm_lane_sample records), parallel to the lane table: row j belongs to lane-table row j
+        self.samples = self._samples_host = None
+        if self.sampling:
+            self.samples = torch.zeros((B, o.SAMPLE_WORDS), dtype=torch.int64, device=dev)
+            self._samples_host = torch.zeros((B, o.SAMPLE_WORDS), dtype=torch.int64)
+            if dev.type == "cuda":
+                self._samples_host = self._samples_host.pin_memory()
         self._graphs = {}
         self.max_graphs = engine.max_graphs
         self._rv = LaneRendezvous(self.n_lanes, lambda reqs: self.generate(reqs, return_exceptions=True))
@@ -208,8 +231,37 @@ class StreamGroup:
         self._table_host[stage_row].copy_(torch.from_numpy(rec))
         self.table[row].copy_(self._table_host[stage_row], non_blocking=True)
 
+    def _sample_record(self, lane: SvlmEngine):
+        """The lane's svlm_lane_sample record from what its `generate_begin` left: `_sampling` (None = greedy) and the seed in `rng_dev`."""
+        if lane._sampling is None:
+            return self.engine.ops.lane_sample_record()
+        t, k, p = lane._sampling
+        return self.engine.ops.lane_sample_record(lane.rng_dev, t, k, p)
+
+    def _write_sample_row(self, row: int, rec: np.ndarray):
+        self._samples_host[row].copy_(torch.from_numpy(rec))
+        self.samples[row].copy_(self._samples_host[row], non_blocking=True)
+
     # ------------------------------------------------------------------ one batched decode step
-    def _step_launch(self, act):
+    def _head(self, tab, B, sampled: bool):
+        """The head and the token feedback.  `sampled`: some lane of the batch draws its token -- the head adds the Gumbel noise where a
+        lane's record asks for it and the finish branches on each lane's mode; an all-greedy batch keeps the greedy pair."""
+        e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
+        if not sampled:
+            if e.llm_fp8:
+                o.decb_lm_head_fp8(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, self.suppress, self.ws)
+            else:
+                o.decb_lm_head(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
+            o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
+            return
+        if e.llm_fp8:
+            o.decb_lm_head_sample_fp8(tab, self.samples, B, self.x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, self.suppress,
+                                      self.ws)
+        else:
+            o.decb_lm_head_sample(tab, self.samples, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
+        o.decb_sample_finish(tab, self.samples, B, self.logits, self.suppress, self.ws, tc.vocab_size, 1)
+
+    def _step_launch(self, act, sampled: bool = False):
         """One token for every live lane of the batch: per layer [norm+QKV+append]xB-in-one, B x [attn split, attn combine],
         [o+res]xB-in-one, [norm+gate/up+SwiGLU]xB-in-one, [down+res]xB-in-one; then the head and the token feedback."""
         e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
@@ -218,7 +270,8 @@ class StreamGroup:
         tab = self.table
         o.decb_embed(tab, B, w.embed, self.x)
         if e.llm_fp8:
-            self._layers_and_head_fp8(act, tab, B, scale)
+            self._layers_fp8(act, tab, B, scale)
+            self._head(tab, B, sampled)
             return
         for li, lw in enumerate(w.layers):
             o.decb_qkv(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
@@ -228,12 +281,11 @@ class StreamGroup:
             o.decb_gemv(tab, B, self.attn, lw["o_w"], self.x, self.x)
             o.decb_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
             o.decb_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
-        o.decb_lm_head(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
-        o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
+        self._head(tab, B, sampled)
 
-    def _layers_and_head_fp8(self, act, tab, B, scale):
-        """The layers and the head of `_step_launch` on e4m3 weights: the same launches with the four weight-streaming kernels replaced by
-        their fp8 twins (csrc/decode_batch_fp8.hip)."""
+    def _layers_fp8(self, act, tab, B, scale):
+        """The layers of `_step_launch` on e4m3 weights: the same launches with the weight-streaming kernels replaced by their fp8 twins
+        (csrc/decode_batch_fp8.hip)."""
         e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
         qd, kd, nl = e.qd, e.kd, len(w.layers)
         for li, lw in enumerate(w.layers):
@@ -244,15 +296,15 @@ class StreamGroup:
             o.decb_gemv_fp8(tab, B, self.attn, lw["o_w8"], lw["o_w_s"], self.x, self.x)
             o.decb_gate_up_fp8(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w8"], lw["gu_w_s"], self.h)
             o.decb_gemv_fp8(tab, B, self.h, lw["down_w8"], lw["down_w_s"], self.x, self.x)
-        o.decb_lm_head_fp8(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, self.suppress, self.ws)
-        o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
 
-    def _step(self, idx, act):
+    def _step(self, idx, act, sampled: bool = False):
         if not self.use_graph:
-            self._step_launch(act)
+            self._step_launch(act, sampled)
             return
-        # keyed on the lanes of the batch, their caches and attention geometry; penalty / suppression / limits live in the lane table
-        key = tuple((i, c.serial, lane.decode_chunk, lane._attn_len) for i, (lane, c) in zip(idx, act))
+        # keyed on the lanes of the batch, their caches and attention geometry, and on whether the step ends in the sampling pair (the
+        # one thing about token choice that changes the launches); penalty / suppression / limits live in the lane table, and each
+        # lane's mode, temperature, k, p and seed pointer in the sampling table
+        key = tuple((i, c.serial, lane.decode_chunk, lane._attn_len) for i, (lane, c) in zip(idx, act)) + (sampled,)
         hit = self._graphs.get(key)
         if hit is not None and any(r() is not c for r, (_, c) in zip(hit[1], act)):
             hit = None
@@ -260,7 +312,7 @@ class StreamGroup:
             g = torch.cuda.CUDAGraph()
             # thread-local capture: other lanes' host threads may be preparing their next chunk (frame ingest) meanwhile
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._step_launch(act)
+                self._step_launch(act, sampled)
             for k in [k for k, v in self._graphs.items() if any(r() is None for r in v[1])]:
                 del self._graphs[k]          # graphs of pools that are gone (a graph must not keep its pools alive)
             if len(self._graphs) >= self.max_graphs:
@@ -281,7 +333,7 @@ class StreamGroup:
             if req is None:
                 continue
             try:
-                ctx = self.lanes[i].generate_begin(**check_request(req))
+                ctx = self.lanes[i].generate_begin(**check_request(req, self.sampling))
             except Exception as e:
                 if not return_exceptions:
                     raise
@@ -295,13 +347,16 @@ class StreamGroup:
         if B:
             for j, ((lane, c), ctx) in enumerate(zip(act, ctxs)):
                 self._write_row(j, self._record(lane, c, ctx.max_new_tokens), j)
+                if self.sampling:
+                    self._write_sample_row(j, self._sample_record(lane))
+            sampled = self.sampling and any(lane._sampling is not None for lane, _ in act)
             n_steps = max(ctx.max_new_tokens for ctx in ctxs) - 1
             done = [False] * B                   # host view: an EOS was seen among the lane's tokens
             polls = [None] * B                   # per lane: (event, host buffer, token count) of the look still in flight
             for step in range(1, n_steps + 1):
                 if not any(step < ctx.max_new_tokens and not done[j] for j, ctx in enumerate(ctxs)):
                     break                        # no lane is live: nothing more to launch
-                self._step(idx, act)
+                self._step(idx, act, sampled)
                 # the single stream's one-poll-behind EOS look, per lane (engine.generate_steps): a lane whose tokens show an EOS is
                 # parked (limit 0 in its table row) for the steps not yet queued; its rows past the EOS are rolled back by its commit
                 if dev_is_gpu and step % 4 == 0 and step + 1 < n_steps + 1:

@@ -17,6 +17,12 @@ is read against the bf16 group and the solo fp8 stream of ONE run, never against
 (csrc/gemm_wfp8.hip), no dequantisation into a scratch layer -- and the groups of the scratch-layer fp8 model ("group_fp8_scratch") run in
 the same process beside the bf16 groups, so direct fp8, scratch fp8 and bf16 groups are all of ONE run.
 
+`--sample T[,K[,P]]` (may be given more than once): after the greedy passes, the same passes with every stream drawing its tokens
+(do_sample=True at temperature T, top_k K -- 0 = off, the default -- and top_p P, a generator seed per stream) through
+`StreamGroup(sampling=True)`, and the solo sampled stream of the same run; per setting and B the decode step is read against the greedy
+group's step, and the solo sampled step against the solo greedy step (the per-token surcharge of the token choice, once per step in a
+group).  Writes profiles/stream_group_sampling_<model>.json.
+
 Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- python tools/stream_group_bench.py --kernels-only`
 (a run of its own, no counters) and pass the stats CSV with --kernel-stats to have the decb_* / single-row averages folded in.
 
@@ -24,6 +30,7 @@ Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- pyth
     python tools/stream_group_bench.py --llm-fp8                                      (writes profiles/stream_group_fp8_2b.json)
     python tools/stream_group_bench.py --llm-fp8 --model 7b --fps 2 --window 4096     (writes profiles/stream_group_fp8_7b.json)
     python tools/stream_group_bench.py --prefill-fp8 [--model 7b --fps 2 --window 4096]  (writes profiles/stream_group_prefill_fp8_<model>.json)
+    python tools/stream_group_bench.py --sample 0.9 --sample 0.9,50,1.0               (writes profiles/stream_group_sampling_2b.json)
 """
 import argparse
 import csv
@@ -96,6 +103,8 @@ def main():
     ap.add_argument("--llm-fp8", action="store_true", help="e4m3 language-model weights: fp8 solo + fp8 groups, and the bf16 groups of the same run")
     ap.add_argument("--prefill-fp8", action="store_true", help="--llm-fp8 with the prefill on the e4m3 weights (prefill_fp8=True); the scratch-layer "
                                                                "fp8 groups and the bf16 groups run in the same process")
+    ap.add_argument("--sample", action="append", default=[], metavar="T[,K[,P]]",
+                    help="also run solo and groups with every stream sampling at temperature T, top_k K (0 = off) and top_p P")
     ap.add_argument("--kernels-only", action="store_true", help="one short pass per B and nothing else (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 kernel_stats CSV of a --kernels-only run")
     ap.add_argument("--fold", default=None, help="with --kernel-stats: add the kernel averages to this earlier record of the same workload "
@@ -103,9 +112,18 @@ def main():
     ap.add_argument("--out", default=None, help="record file; --llm-fp8 timed runs default to profiles/stream_group_fp8_<model>.json")
     args = ap.parse_args()
     args.llm_fp8 = args.llm_fp8 or args.prefill_fp8
+    settings = []
+    for spec in args.sample:
+        f = spec.split(",")
+        if not 1 <= len(f) <= 3:
+            ap.error(f"--sample {spec}: T[,K[,P]]")
+        settings.append((float(f[0]), int(f[1]) if len(f) > 1 else 0, float(f[2]) if len(f) > 2 else 1.0))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if settings and not args.kernels_only and not args.fold and args.out is None:
+        args.out = os.path.join(root, "profiles", f"stream_group_sampling_{args.model}.json")
     if args.llm_fp8 and not args.kernels_only and not args.fold and args.out is None:
         stem = "stream_group_prefill_fp8" if args.prefill_fp8 else "stream_group_fp8"
-        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"{stem}_{args.model}.json")
+        args.out = os.path.join(root, "profiles", f"{stem}_{args.model}.json")
 
     cfg = {"2b": C.qwen2_vl_2b, "7b": C.qwen2_vl_7b, "tiny": C.tiny}[args.model]()
     if args.fold:
@@ -130,12 +148,15 @@ def main():
     base = "Qwen2"
     torch.set_num_threads(min(torch.get_num_threads(), 8))
 
-    def stream_kw(seed):
+    def stream_kw(seed, sample=None):
         video = ResidentVideo(n_chunks + 1, args.size, args.fps, seed, dev)
-        return dict(video=video, model_base=base, duration=n_chunks, previous_text="", kv_policy="sink_window", sink=args.sink,
-                    window=args.window, do_sample=False, max_new_tokens=args.new_tokens, suppress_eos=True, quiet=True)
+        kw = dict(video=video, model_base=base, duration=n_chunks, previous_text="", kv_policy="sink_window", sink=args.sink,
+                  window=args.window, do_sample=False, max_new_tokens=args.new_tokens, suppress_eos=True, quiet=True)
+        if sample is not None:
+            kw.update(do_sample=True, temperature=sample[0], top_k=sample[1], top_p=sample[2], generator=torch.Generator().manual_seed(1000 + seed))
+        return kw
 
-    def timed(run, streams, lookahead):
+    def timed(run, streams, lookahead, sample=None):
         """`run(streams, callbacks)`; the clock runs from the chunk `fill` of stream 0 (every stream has then filled its window: they
         advance in lock-step) to the end; returns ms per chunk-round."""
         t = {}
@@ -144,7 +165,7 @@ def main():
             if i == fill:
                 torch.cuda.synchronize()
                 t["t0"] = time.perf_counter()
-        kws = [dict(stream_kw(s), vision_lookahead=lookahead) for s in range(streams)]
+        kws = [dict(stream_kw(s, sample), vision_lookahead=lookahead) for s in range(streams)]
         kws[0]["chunk_callback"] = cb
         counts = [[] for _ in kws]
         for kw, c in zip(kws, counts):
@@ -186,11 +207,11 @@ def main():
         out["solo_lookahead"] = timed(solo_run, 1, True)
         out["solo"]["decode_ms_per_chunk"] = replay_decode(eng._graph, [eng], args.new_tokens - 1)       # (its cache is still eng._last_cache)
 
-    def group_passes(m):
+    def group_passes(m, sample=None):
         groups = {}
         for B in range(1, args.max_lanes + 1):
-            group = StreamGroup(m._svlm_engine, B)
-            rec = timed(lambda kws: S.streaming_inference_group(m, proc, kws, group=group), B, False)
+            group = StreamGroup(m._svlm_engine, B, sampling=sample is not None)
+            rec = timed(lambda kws: S.streaming_inference_group(m, proc, kws, group=group), B, False, sample)
             # the decode steps alone: the batched step graph of the last batch, one chunk's worth of replays per round
             rec["decode_ms_per_chunk"] = replay_decode(next(reversed(group._graphs.values()))[0], group.lanes, args.new_tokens - 1)
             rec["decode_us_per_step"] = 1e3 * rec["decode_ms_per_chunk"] / (args.new_tokens - 1)
@@ -229,6 +250,27 @@ def main():
             # the only margin: the solo repeats' own spread, as frames/s
             fps_solo = [p["frames_per_sec"] for p in out["solo"]["passes"]]
             out["best"].update(solo_fp8_frames_per_sec=ref, solo_fp8_frames_per_sec_spread=max(fps_solo) - min(fps_solo))
+    if settings:
+        # every stream draws its tokens: the solo sampled stream and the sampling groups of the same process and run, each read against
+        # its greedy counterpart above
+        n_dec = args.new_tokens - 1
+        out["sampling"] = {}
+        for t, k, p in settings:
+            rec = out["sampling"][f"T={t:g},top_k={k},top_p={p:g}"] = dict(temperature=t, top_k=k, top_p=p)
+            if "solo" in out:
+                passes = [timed(solo_run, 1, False, (t, k, p)) for _ in range(args.repeats)]
+                fps = [q["frames_per_sec"] for q in passes]
+                rec["solo"] = dict(passes=passes, frames_per_sec_median=statistics.median(fps), frames_per_sec_spread=max(fps) - min(fps),
+                                   decode_ms_per_chunk=replay_decode(eng._graph, [eng], n_dec))
+                rec["solo"]["decode_us_per_step"] = 1e3 * rec["solo"]["decode_ms_per_chunk"] / n_dec
+                rec["solo"]["surcharge_us_per_step"] = rec["solo"]["decode_us_per_step"] - 1e3 * out["solo"]["decode_ms_per_chunk"] / n_dec
+            rec["group"] = group_passes(model, (t, k, p))
+            for B, g in rec["group"].items():
+                g["surcharge_us_per_step_vs_greedy_group"] = g["decode_us_per_step"] - groups[B]["decode_us_per_step"]
+                g["frames_per_sec_vs_greedy_group"] = g["frames_per_sec"] / groups[B]["frames_per_sec"]
+                if "solo" in rec:
+                    g["aggregate_frames_per_sec_vs_solo_sampled"] = g["frames_per_sec"] / rec["solo"]["frames_per_sec_median"]
+                    g["surcharge_vs_solo_surcharge"] = g["surcharge_us_per_step_vs_greedy_group"] / rec["solo"]["surcharge_us_per_step"]
     if args.kernel_stats:
         out["kernel_stats"] = kernel_stats(args.kernel_stats, cfg)
     text = json.dumps(out, indent=1)
