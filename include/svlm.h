@@ -332,6 +332,27 @@ int svlm_gemm_wfp8_norm(const void* A, int lda, const void* W8, int ldw, const f
                         int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, const void* norm_w,
                         const void* norm_b, float eps, void* XN, int ldxn, void* stream);
 
+/* ---- opt-in MXFP4 language-model weights (csrc/decode_fp4.hip; SvlmEngine(llm_fp4=True)).  W4 holds OCP e2m1 codes, two per byte
+ * (element 2i of a row in the low nibble of byte i, rows of ldw BYTES), w_scale one e8m0 byte per block of 32 K elements (byte b stands
+ * for 2^(b - 127); [N, K / 32] row-major, contiguous: weights.py:quantize_blocks_mxfp4).  W' = code * 2^e is exact in bf16.  Each entry
+ * is its fp8 / bf16 twin with W4 + w_scale in place of the weights: same prologue, epilogue and rounding points, the scale applied inside
+ * the conversion, so each computes the bf16 entry on W' up to the fp32 summation order.  K a multiple of 32 (one 16-B load = 32 codes =
+ * one block), ldw a multiple of 16.  The lm_head of such an engine stays e4m3 (svlm_dec_lm_head[_sample]_fp8, svlm_gemv_fp8).
+ * replaces: qwen2/language_forward.py:183,80-82 + generate/streaming_cache.py:72-73 (as svlm_dec_qkv_fp8). */
+int svlm_dec_qkv_fp4(const void* x, const void* ln_w, float eps, const void* W4, int ldw, const void* w_scale, const void* bias,
+                     void* q_out, void* k_planes, void* v_planes, const int* slot_of, const int* len_dev, int len_host, int K, int qd,
+                     int kd, int D, int n_slots, void* k_lin, void* v_lin, int lin_rows, void* stream);
+/* replaces: qwen2/language_forward.py:200-201 (Qwen2MLP gate/up + SwiGLU, as svlm_dec_gate_up_fp8). */
+int svlm_dec_gate_up_fp4(const void* x, const void* ln_w, float eps, const void* W4, int ldw, const void* w_scale, void* h, int I, int K,
+                         void* stream);
+/* y = bf16(W' x + bias) (+ residual, rounded again), y_f32 = the same value in fp32; act must be 0 (none).
+ * replaces: o_proj / down_proj at T = 1 (qwen2/language_forward.py:161,201). */
+int svlm_gemv_fp4(const void* x, const void* W4, int ldw, const void* w_scale, const void* bias, const void* residual, void* y,
+                  float* y_f32, int N, int K, int act, void* stream);
+/* dst[r, c] = bf16(code[r, c] * 2^e[r, c / 32]) for contiguous [rows, cols] matrices (cols a multiple of 32): the bf16 image W' of one
+ * layer, which the prefill GEMMs read.  replaces: nothing (the reference has bf16 weights; this rebuilds them from the fp4 copy). */
+int svlm_dequant_fp4_bf16(const void* src4, const void* scale, void* dst, int rows, int cols, void* stream);
+
 /* ---- stream groups: lane-batched decode step (csrc/decode_batch.hip; stream_group.py).  B = 1..4 independent streams ("lanes") on
  * one GPU and ONE weight set take their decode step together: every kernel below reads each weight row once and multiplies it with the
  * B activation rows of the group.  Per (lane, output row) the FMA order, the reductions and every bf16 rounding point are those of the

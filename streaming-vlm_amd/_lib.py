@@ -81,6 +81,10 @@ SIGNATURES = {
     "svlm_dequant_fp8_bf16": (_i, [_p, _p, _p, _i, _i, _p]),
     "svlm_gemm_wfp8": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "svlm_gemm_wfp8_norm": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _f, _p, _i, _p]),
+    "svlm_dec_qkv_fp4": (_i, [_p, _p, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "svlm_dec_gate_up_fp4": (_i, [_p, _p, _f, _p, _i, _p, _p, _i, _i, _p]),
+    "svlm_gemv_fp4": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "svlm_dequant_fp4_bf16": (_i, [_p, _p, _p, _i, _i, _p]),
     "svlm_decb_embed": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
     "svlm_decb_qkv": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "svlm_decb_gate_up": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p]),

@@ -1,0 +1,57 @@
+// MXFP4 weight-stream pieces of the fp4 decode kernels (decode_fp4.hip): OCP e2m1 codes, two per byte (element 2i in the low nibble of
+// byte i), one e8m0 scale byte per block of 32 consecutive K elements in an array of its own (row-major, K / 32 per row).  A K-step is
+// 2048 elements, 32 consecutive ones per lane: one 16-B load = 32 codes = exactly one block, so a lane needs one scale byte per load.
+#pragma once
+#include "common.h"
+#include "dec_fp8.h"              // x16, f32x2_t
+
+typedef uint8_t fp4x2_t;          // two e2m1 codes
+typedef uint8_t e8m0_t;           // scale byte b: 2^(b - 127)
+
+// the scale as the float the conversion multiplies with: a normal fp32 for every byte in [1, 254]
+__device__ __forceinline__ float e8m0_f32(unsigned b) { return __uint_as_float(b << 23); }
+
+// acc += sum_j e2m1(code j of w0 | w1) * s * xf[j], j = 0..15 in element order.  v_cvt_scalef32_pk_f32_fp4 turns one byte (two codes,
+// low nibble first) into two fp32 already multiplied by s: exact, s being a power of two and a code having 2 significant bits.
+__device__ __forceinline__ float dot16_fp4(unsigned w0, unsigned w1, float s, const float (&xf)[16], float acc) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const unsigned w = h ? w1 : w0;
+    const f32x2_t a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 0);
+    const f32x2_t b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 1);
+    const f32x2_t c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 2);
+    const f32x2_t d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 3);
+    acc = fmaf(a[0], xf[8 * h], acc);
+    acc = fmaf(a[1], xf[8 * h + 1], acc);
+    acc = fmaf(b[0], xf[8 * h + 2], acc);
+    acc = fmaf(b[1], xf[8 * h + 3], acc);
+    acc = fmaf(c[0], xf[8 * h + 4], acc);
+    acc = fmaf(c[1], xf[8 * h + 5], acc);
+    acc = fmaf(d[0], xf[8 * h + 6], acc);
+    acc = fmaf(d[1], xf[8 * h + 7], acc);
+  }
+  return acc;
+}
+
+// PRE K-steps of NR rows in flight: per (K-step, row) one 16-B load of codes and one scale byte
+template <int NR, int PRE>
+struct W4Pre {
+  u32x4_t w[PRE][NR];
+  unsigned s[PRE][NR];
+};
+// wr[r] / sr[r]: the row's codes and scale bytes; K / 32 blocks per row
+template <int NR, int PRE>
+__device__ __forceinline__ void preload_w4(const fp4x2_t* const (&wr)[NR], const e8m0_t* const (&sr)[NR], int base, int K,
+                                           W4Pre<NR, PRE>& pre) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int it = 0; it < PRE; ++it) {
+    const int c = base + it * 2048 + lane * 32;
+    const int cc = c < K ? c : 0;                            // clamped (valid) address; its product is masked out
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      pre.w[it][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr[r] + (cc >> 1)));
+      pre.s[it][r] = sr[r][cc >> 5];
+    }
+  }
+}

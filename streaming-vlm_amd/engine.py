@@ -34,6 +34,8 @@ BF16 = torch.bfloat16
 FP8_LLM_OPS = ("dec_qkv_fp8", "dec_gate_up_fp8", "gemv_fp8", "dec_lm_head_fp8", "dequant_fp8")
 # ... and a prefill_fp8 engine on top of them (csrc/gemm_wfp8.hip)
 FP8_PREFILL_OPS = ("gemm_wfp8", "gemm_wfp8_norm")
+# ops entry points an llm_fp4 engine needs (csrc/decode_fp4.hip, and the fp8 head pair of csrc/decode_fp8.hip)
+FP4_LLM_OPS = ("dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4", "dequant_fp4", "gemv_fp8", "dec_lm_head_fp8")
 
 
 @dataclass
@@ -251,7 +253,7 @@ class SvlmEngine:
                  decode_chunk: Optional[int] = None, use_graph: Optional[bool] = None, kv_slack: float = 1.0, kv_page_tokens: int = 16,
                  decode_tail: Optional[bool] = None,
                  vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None,
-                 prefill_fp8: bool = False):
+                 prefill_fp8: bool = False, llm_fp4: bool = False):
         """`share`: another engine of the same model whose WEIGHTS this one uses (language model, vision tower, embedding, lm_head,
         rope frequencies, fp8 vision images): `state_dict` is ignored and no weight tensor is copied; every per-stream buffer (sampling
         state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py).
@@ -259,11 +261,14 @@ class SvlmEngine:
         prefill one after another, as a stream group does; a prefill issued on another stream than the last one waits for that stream
         first (`_dequant_layer`), two prefills issued concurrently from two host threads are not supported.
         `prefill_fp8` (with `llm_fp8`): the prefill GEMMs read the e4m3 matrices themselves (`gemm_wfp8`, csrc/gemm_wfp8.hip): no
-        dequantisation launch, no scratch layer, nothing shared between the prefills of engines that share weights."""
+        dequantisation launch, no scratch layer, nothing shared between the prefills of engines that share weights.
+        `llm_fp4`: the layer matrices as OCP MXFP4 (e2m1 codes + one e8m0 scale per 32 weights), the lm_head e4m3 as with `llm_fp8`; the
+        decode step streams them through the fp4 GEMVs (csrc/decode_fp4.hip), the prefill goes through the scratch layer, shared under
+        the same rule.  Not with `llm_fp8`, `prefill_fp8` or `decode_tail`."""
         if share is not None:
             if (share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8
-                    or bool(prefill_fp8) != share.prefill_fp8):
-                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, prefill_fp8 and vit_fp8")
+                    or bool(prefill_fp8) != share.prefill_fp8 or bool(llm_fp4) != share.llm_fp4):
+                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, llm_fp4, prefill_fp8 and vit_fp8")
             ops = share.ops if ops is None else ops
         if ops is None:
             from .ops import HipOps
@@ -297,8 +302,21 @@ class SvlmEngine:
             for name, K in (("hidden", tc_.hidden_size), ("q width", tc_.num_heads * tc_.head_dim), ("intermediate", tc_.intermediate_size)):
                 if K % 64:
                     raise ValueError(f"prefill_fp8=True needs every GEMM K to be a multiple of 64 (one K-tile of the kernel): {name} is {K}")
-        self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8)
-        self._fp8_scratch = None           # llm_fp8: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
+        # opt-in MXFP4 language model: the layer matrices as e2m1 codes with one power-of-two scale per block of 32 (weights.py:
+        # quantize_blocks_mxfp4), the lm_head e4m3.  It computes exactly the bf16 model on W' = weights.fp4_reference_state_dict(state_dict).
+        self.llm_fp4 = bool(llm_fp4)
+        if self.llm_fp4:
+            if self.llm_fp8 or self.prefill_fp8:
+                raise ValueError("llm_fp4=True cannot be combined with llm_fp8=True / prefill_fp8=True (two formats of the same matrices; "
+                                 "the weight-fp8 prefill GEMMs read e4m3 codes)")
+            missing = [m for m in FP4_LLM_OPS if not hasattr(ops, m)]
+            if missing:
+                raise ValueError(f"llm_fp4=True needs an ops backend with the fp4 entry points; {type(ops).__name__} lacks {missing}")
+            if decode_tail or (decode_tail is None and os.environ.get("SVLM_DECODE_TAIL", "0") == "1"):
+                raise ValueError("llm_fp4=True cannot be combined with decode_tail=True (the persistent layer tail streams bf16 weights)")
+        self._head_fp8 = self.llm_fp8 or self.llm_fp4          # the lm_head is e4m3 in both
+        self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8, llm_fp4=self.llm_fp4)
+        self._fp8_scratch = None           # llm_fp8 / llm_fp4: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
         self._fp8_scratch_owner = share._fp8_scratch_owner if share is not None else self      # whose scratch layer this engine uses
         if share is not None:
             self._fp8_scratch_owner._fp8_scratch_shared = True
@@ -613,7 +631,7 @@ class SvlmEngine:
                 else:
                     o.gemm_wfp8(hm, lw["down_w8"], lw["down_w_s"], residual=x, out=x)
                 continue
-            if self.llm_fp8:
+            if self.llm_fp8 or self.llm_fp4:
                 lw = self._dequant_layer(lw)
             o.gemm(xn, lw["qkv_w"], bias=lw["qkv_b"], out=qkv)
             # the chunk's K/V rows go to their pool slots inside the launch that rotates and gathers the keys
@@ -639,13 +657,13 @@ class SvlmEngine:
             return
         last = x[T - 1:T].contiguous()
         o.rmsnorm(last, w.final_norm, tc.rms_eps, out=self.d_xn.view(1, H))
-        if self.llm_fp8:
+        if self._head_fp8:
             o.gemv_fp8(self.d_xn, w.lm_head8, w.lm_head_s, out_f32=self.logits)
         else:
             o.gemv(self.d_xn, w.lm_head, out_f32=self.logits)
 
     def _dequant_layer(self, lw):
-        """llm_fp8 prefill: the layer's four matrices as bf16 W' in the (reused) scratch layer; the layer dict with those views."""
+        """llm_fp8 / llm_fp4 prefill: the layer's four matrices as bf16 W' in the (reused) scratch layer; the layer dict with those views."""
         # Engines that share weights (share=: the lanes of a stream group) share the ONE scratch layer of the engine that owns the
         # weights.  That is safe because a group's prefills never overlap: `StreamGroup.generate` calls the lanes' `generate_begin`
         # one after another from the one thread that issues the batch, every launch of a prefill -- the dequantisation and the GEMMs
@@ -659,16 +677,20 @@ class SvlmEngine:
                 stream.wait_stream(last)
             own._fp8_scratch_stream = stream
         sc = self._fp8_scratch = own._fp8_scratch
+        fp4 = self.llm_fp4
         if sc is None:
-            flat = torch.empty(lw["flat8"].numel(), dtype=BF16, device=self.device)
+            flat = torch.empty(lw["flat4"].numel() * 2 if fp4 else lw["flat8"].numel(), dtype=BF16, device=self.device)
             sc, off = {}, 0
             for name in ("qkv_w", "o_w", "gu_w", "down_w"):
-                n = lw[name + "8"].numel()
-                sc[name] = flat[off:off + n].view(lw[name + "8"].shape)
-                off += n
+                N, K = (lw[name + "4"].shape[0], lw[name + "4"].shape[1] * 2) if fp4 else lw[name + "8"].shape
+                sc[name] = flat[off:off + N * K].view(N, K)
+                off += N * K
             self._fp8_scratch = own._fp8_scratch = sc
         for name, dst in sc.items():
-            self.ops.dequant_fp8(lw[name + "8"], lw[name + "_s"], dst)
+            if fp4:
+                self.ops.dequant_fp4(lw[name + "4"], lw[name + "_s4"], dst)
+            else:
+                self.ops.dequant_fp8(lw[name + "8"], lw[name + "_s"], dst)
         return dict(lw, **sc)
 
     def _decode_step_launch(self, c: KVPool):
@@ -694,7 +716,7 @@ class SvlmEngine:
                     ln = w.layers[li + 1]
                     nxt = (ln["ln1"], ln["qkv_w"], ln["qkv_b"], self.d_qkv, c.pool, li + 1, c.slot_of_dev, qd, kd, 0, kv_len)
                 o.dec_tail(self.d_attn, self.d_x, lw["o_w"], lw["ln2"], lw["gu_w"], lw["down_w"], tc.rms_eps, self.tail_ws, li, nl, nxt=nxt)
-        for li, lw in enumerate(w.layers if not (self.decode_tail or self.llm_fp8) else ()):
+        for li, lw in enumerate(w.layers if not (self.decode_tail or self.llm_fp8 or self.llm_fp4) else ()):
             o.dec_qkv(self.d_x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.d_qkv, c.pool, li, c.slot_of_dev, qd, kd,
                       len_dev=kv_len, lin=lin)
             o.decode_attn(self.d_qkv[:qd], c.pool, li, c.slot_of_dev, self.rope_cs, self.d_attn, self.d_ws, tc.num_heads,
@@ -711,9 +733,18 @@ class SvlmEngine:
             o.gemv_fp8(self.d_attn, lw["o_w8"], lw["o_w_s"], residual=self.d_x, out=self.d_x)
             o.dec_gate_up_fp8(self.d_x, lw["ln2"], tc.rms_eps, lw["gu_w8"], lw["gu_w_s"], self.d_h)
             o.gemv_fp8(self.d_h, lw["down_w8"], lw["down_w_s"], residual=self.d_x, out=self.d_x)
+        for li, lw in enumerate(w.layers if self.llm_fp4 else ()):
+            # ... and on MXFP4 weights (csrc/decode_fp4.hip); the head below is the fp8 one
+            o.dec_qkv_fp4(self.d_x, lw["ln1"], tc.rms_eps, lw["qkv_w4"], lw["qkv_w_s4"], lw["qkv_b"], self.d_qkv, c.pool, li, c.slot_of_dev, qd, kd,
+                          len_dev=kv_len, lin=lin)
+            o.decode_attn(self.d_qkv[:qd], c.pool, li, c.slot_of_dev, self.rope_cs, self.d_attn, self.d_ws, tc.num_heads,
+                          self._attn_len, self.decode_chunk, scale, length=1, len_dev=kv_len, lin=lin)
+            o.gemv_fp4(self.d_attn, lw["o_w4"], lw["o_w_s4"], residual=self.d_x, out=self.d_x)
+            o.dec_gate_up_fp4(self.d_x, lw["ln2"], tc.rms_eps, lw["gu_w4"], lw["gu_w_s4"], self.d_h)
+            o.gemv_fp4(self.d_h, lw["down_w4"], lw["down_w_s4"], residual=self.d_x, out=self.d_x)
         smp = self._sampling
         seen = self.seen if self._penalty != 1.0 else None
-        if self.llm_fp8:
+        if self._head_fp8:
             head = lambda **kw: o.dec_lm_head_fp8(self.d_x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, seen, self._penalty,
                                                   self._suppress, self.d_sws, **kw)
         else:

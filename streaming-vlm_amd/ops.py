@@ -931,6 +931,67 @@ class HipOps:
         self._check(self.lib.svlm_dequant_fp8_bf16(_ptr(W8), _ptr(w_scale), _ptr(out), N, K, _stream()), "svlm_dequant_fp8_bf16")
         return out
 
+    # ------------------------------------------------------------------ MXFP4 language-model weights (csrc/decode_fp4.hip)
+    @staticmethod
+    def _req_fp4(W4, scale, name):
+        """W4: uint8 [N, K / 2] (two e2m1 codes per byte), scale: uint8 [N, K / 32] (e8m0), contiguous.  Returns (N, K)."""
+        _req(W4, torch.uint8, f"{name}.W4", 2); _req(scale, torch.uint8, f"{name}.w_scale", 2)
+        N, K = W4.shape[0], W4.shape[1] * 2
+        if K % 32 or W4.stride(0) % 16 or tuple(scale.shape) != (N, K // 32) or not scale.is_contiguous():
+            raise _lib.SvlmError(f"{name}: W4 {tuple(W4.shape)} (stride {W4.stride(0)}) needs K = 2 x columns a multiple of 32, a row stride "
+                                 f"that is a multiple of 16 and contiguous scales [N, K / 32] (got {tuple(scale.shape)})")
+        return N, K
+
+    def dec_qkv_fp4(self, x, ln_w, eps, W4, w_scale, bias, q_out, pool, layer, slot_of, qd, kd, length=0, len_dev=None, lin=None):
+        """dec_qkv on MXFP4 rows (e2m1 codes + one e8m0 scale per block of 32)."""
+        _req(x, BF16, "dec_qkv_fp4.x", 1); _req(ln_w, BF16, "dec_qkv_fp4.ln_w", 1)
+        _req(bias, BF16, "dec_qkv_fp4.bias", 1); _req(q_out, BF16, "dec_qkv_fp4.q_out", 1); _req(slot_of, torch.int32, "dec_qkv_fp4.slot_of", 1)
+        N, K = self._req_fp4(W4, w_scale, "dec_qkv_fp4")
+        _, _, Hkv, n_slots, D = pool.shape
+        assert N == qd + 2 * kd == bias.numel() and kd == Hkv * D and x.numel() == K == ln_w.numel() and q_out.numel() >= qd
+        if len_dev is None:
+            assert 0 <= length < slot_of.numel()
+        kp, vp = self._planes(pool, layer)
+        kl, vl, lin_rows, _ = self._lin_args(lin, layer, Hkv, D, length + 1 if len_dev is None else 1, "dec_qkv_fp4")
+        self._check(self.lib.svlm_dec_qkv_fp4(_ptr(x), _ptr(ln_w), float(eps), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias), _ptr(q_out), _ptr(kp),
+                                        _ptr(vp), _ptr(slot_of), _ptr(len_dev), int(length), K, qd, kd, D, n_slots, _ptr(kl), _ptr(vl), lin_rows,
+                                        _stream()), "svlm_dec_qkv_fp4")
+
+    def dec_gate_up_fp4(self, x, ln_w, eps, W4, w_scale, h):
+        _req(x, BF16, "dec_gate_up_fp4.x", 1); _req(ln_w, BF16, "dec_gate_up_fp4.ln_w", 1); _req(h, BF16, "dec_gate_up_fp4.h", 1)
+        N, K = self._req_fp4(W4, w_scale, "dec_gate_up_fp4")
+        assert N % 2 == 0 and h.numel() == N // 2 and x.numel() == K == ln_w.numel()
+        self._check(self.lib.svlm_dec_gate_up_fp4(_ptr(x), _ptr(ln_w), float(eps), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(h), N // 2, K, _stream()),
+              "svlm_dec_gate_up_fp4")
+
+    def gemv_fp4(self, x, W4, w_scale, bias=None, residual=None, out=None, out_f32=None):
+        _req(x, BF16, "gemv_fp4.x")
+        N, K = self._req_fp4(W4, w_scale, "gemv_fp4")
+        if x.numel() != K:
+            raise _lib.SvlmError(f"gemv_fp4: x has {x.numel()} elements, W4 is {N} x {K}")
+        if out is None and out_f32 is None:
+            out = torch.empty((N,), dtype=BF16, device=x.device)
+        if out is not None:
+            _req(out, BF16, "gemv_fp4.out"); assert out.numel() == N
+        if out_f32 is not None:
+            _req(out_f32, torch.float32, "gemv_fp4.out_f32"); assert out_f32.numel() == N
+        if bias is not None:
+            _req(bias, BF16, "gemv_fp4.bias"); assert bias.numel() == N
+        if residual is not None:
+            _req(residual, BF16, "gemv_fp4.residual"); assert residual.numel() == N
+        self._check(self.lib.svlm_gemv_fp4(_ptr(x), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), _ptr(out), _ptr(out_f32),
+                                     N, K, ACT_NONE, _stream()), "svlm_gemv_fp4")
+        return out if out is not None else out_f32
+
+    def dequant_fp4(self, W4, w_scale, out):
+        """out = bf16(code * 2^e) = W' (exact); contiguous matrices, out [N, K] for W4 [N, K / 2]."""
+        N, K = self._req_fp4(W4, w_scale, "dequant_fp4")
+        _req(out, BF16, "dequant_fp4.out", 2)
+        if tuple(out.shape) != (N, K) or not W4.is_contiguous() or not out.is_contiguous():
+            raise _lib.SvlmError(f"dequant_fp4: out {tuple(out.shape)} vs W4 {N} x {K}, both contiguous")
+        self._check(self.lib.svlm_dequant_fp4_bf16(_ptr(W4), _ptr(w_scale), _ptr(out), N, K, _stream()), "svlm_dequant_fp4_bf16")
+        return out
+
     # ------------------------------------------------------------------ prefill GEMMs on the e4m3 weights (csrc/gemm_wfp8.hip)
     def gemm_wfp8(self, A, W8, w_scale, bias=None, residual=None, out=None, act=ACT_NONE):
         """`gemm` on W' = W8 * w_scale[:, None] read straight from the codes (no bf16 image of W); K % 64 == 0."""

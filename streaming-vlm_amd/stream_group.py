@@ -171,6 +171,8 @@ class StreamGroup:
             if sampling and not hasattr(engine.ops, "decb_lm_head_sample_fp8"):
                 raise ValueError(f"stream group: sampling=True on an llm_fp8=True engine needs an ops backend with the lane-batched fp8 "
                                  f"sampling head; {type(engine.ops).__name__} lacks decb_lm_head_sample_fp8")
+        if getattr(engine, "llm_fp4", False):
+            raise ValueError("stream group: llm_fp4=True engines are not supported (there are no lane-batched fp4 decode kernels)")
         if getattr(engine, "decode_tail", False):
             raise ValueError("stream group: decode_tail=True engines are not supported (the persistent layer tail is single-row)")
         self.engine = engine

@@ -170,15 +170,75 @@ def fp8_reference_state_dict(sd: Dict[str, torch.Tensor], cfg: ModelConfig) -> D
     return out
 
 
+# OCP MX FP4: a nibble is sign + e2m1; the magnitudes of codes 0..7
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_blocks_mxfp4(w: torch.Tensor):
+    """OCP MXFP4 of a [N, K] matrix, K a multiple of 32: per block of 32 consecutive K elements one scale 2^e with e the smallest integer
+    such that amax(block) <= 6 * 2^e (taken from the fp32 exponent and mantissa of amax, no division: nothing ever saturates), an
+    all-zero block e = 0, e clamped below at -125 (smaller blocks round toward zero and every non-zero W' stays a normal bf16), e > 125
+    a ValueError; codes = round-to-nearest-even of w / 2^e onto the e2m1 grid (0, 0.5, 1, 1.5, 2, 3, 4, 6; a tie goes to the even code),
+    a zero always +0.  Returns (codes uint8 [N, K / 2], scales uint8 [N, K / 32]): element 2i of a row is the low nibble of byte i,
+    element 2i + 1 the high one; scale byte = e + 127 (e8m0; 0xFF is never produced).  W' = code * 2^e is exactly representable in bf16."""
+    if w.dim() != 2 or w.shape[1] % 32:
+        raise ValueError(f"quantize_blocks_mxfp4: needs a [N, K] matrix with K a multiple of 32 (one block = 32 elements), got {tuple(w.shape)}")
+    N, K = w.shape
+    wf = w.detach().float().view(N, K // 32, 32)
+    amax = wf.abs().amax(dim=2)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_blocks_mxfp4: non-finite weights")
+    m, ex = torch.frexp(amax)                                # amax = m * 2^ex, m in [0.5, 1); 6 * 2^e = 0.75 * 2^(e + 3)
+    e = torch.where(m <= 0.75, ex - 3, ex - 2)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    if int(e.max()) > 125:
+        raise ValueError("quantize_blocks_mxfp4: a block needs a scale above 2^125")
+    e = e.clamp(min=-125)
+    a = torch.ldexp(wf.abs(), -e.unsqueeze(2))               # |w| / 2^e <= 6, exact (a power-of-two factor)
+    # the grid's step is 0.5 below 2, 1 up to 4, 2 up to 6; torch.round is half-to-even and an even multiple of the step is an even code
+    q = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    code = torch.where(q <= 2, q * 2, torch.where(q <= 4, q + 2, torch.full_like(q, 7.0))).to(torch.uint8)
+    code = torch.where((wf < 0) & (q > 0), code | 8, code).view(N, K)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return codes, (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_blocks_mxfp4(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16):
+    """W' = e2m1(code) * 2^(scale - 127), [N, K] from codes [N, K / 2] and scales [N, K / 32] (exact in bf16)."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    vals = torch.stack([lut[(codes & 0xF).long()], lut[(codes >> 4).long()]], dim=-1).view(N, K // 32, 32)
+    return torch.ldexp(vals, (scales.to(torch.int32) - 127).unsqueeze(2)).view(N, K).to(dtype)
+
+
+def fp4_reference_state_dict(sd: Dict[str, torch.Tensor], cfg: ModelConfig) -> Dict[str, torch.Tensor]:
+    """The model an `llm_fp4=True` engine built from `sd` computes, as a bf16 state dict: every LLM layer matrix (q/k/v/o_proj,
+    gate/up/down_proj) replaced by its MXFP4 W' = dequant(quant(W)), the lm_head by its e4m3 W' exactly as `fp8_reference_state_dict`
+    does it (the head of an fp4 engine stays e4m3).  Everything else stays as it is."""
+    tc = cfg.text
+    out = dict(sd)
+    for i in range(tc.num_layers):
+        for m in LLM_FP8_MATRICES:
+            k = f"{L_PREFIX}layers.{i}.{m}.weight"
+            out[k] = dequantize_blocks_mxfp4(*quantize_blocks_mxfp4(sd[k]), dtype=sd[k].dtype)
+    head = sd[L_PREFIX + "embed_tokens.weight"] if tc.tie_word_embeddings else sd["lm_head.weight"]
+    out["lm_head.weight"] = dequantize_rows_fp8(*quantize_rows_fp8_pow2(head), dtype=head.dtype)
+    return out
+
+
 class EngineWeights:
     """Fused, contiguous, device-resident views the kernels consume.
 
     `llm_fp8`: the LLM layer matrices and the lm_head are kept as e4m3 with one power-of-two scale per row (quantize_rows_fp8_pow2),
     quantised layer by layer so that no bf16 copy of all layers ever exists; per layer `flat8` (qkv | o | gate/up | down, back to
     back) and `scale` (their rows' scales, same order) with the views `<name>8` / `<name>_s`; `lm_head8` / `lm_head_s`.  The bf16
-    embedding table stays."""
+    embedding table stays.
 
-    def __init__(self, sd: Dict[str, torch.Tensor], cfg: ModelConfig, device, llm_fp8: bool = False):
+    `llm_fp4`: the layer matrices are kept as OCP MXFP4 (quantize_blocks_mxfp4), again one matrix at a time; per layer `flat4` (the codes
+    of qkv | o | gate/up | down, back to back) and `scale4` (their block scales, same order) with the views `<name>4` [N, K / 2] and
+    `<name>_s4` [N, K / 32]; the lm_head is e4m3 as with `llm_fp8` (`lm_head8` / `lm_head_s`)."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], cfg: ModelConfig, device, llm_fp8: bool = False, llm_fp4: bool = False):
         vc, tc = cfg.vision, cfg.text
         want = state_dict_shapes(cfg)
         missing = [k for k in want if k not in sd]
@@ -224,11 +284,14 @@ class EngineWeights:
             self.merger = {k: dev(sd[m + n]) for k, n in [("ln_w", "ln_q.weight"), ("ln_b", "ln_q.bias"), ("w0", "mlp.0.weight"),
                                                            ("b0", "mlp.0.bias"), ("w2", "mlp.2.weight"), ("b2", "mlp.2.bias")]}
         self.embed = dev(sd[L_PREFIX + "embed_tokens.weight"])
-        self.llm_fp8 = bool(llm_fp8)
-        if self.llm_fp8:
+        self.llm_fp8, self.llm_fp4 = bool(llm_fp8), bool(llm_fp4)
+        if self.llm_fp8 and self.llm_fp4:
+            raise ValueError("llm_fp8 and llm_fp4 are two formats of the same matrices: choose one")
+        if self.llm_fp8 or self.llm_fp4:
+            need, why = (32, "one MX block = 32 weights") if self.llm_fp4 else (16, "one 16-B load = 16 weights")
             for name, K in (("hidden", tc.hidden_size), ("q width", tc.num_heads * tc.head_dim), ("intermediate", tc.intermediate_size)):
-                if K % 16:
-                    raise ValueError(f"llm_fp8 needs K a multiple of 16 (one 16-B load = 16 weights): {name} is {K}")
+                if K % need:
+                    raise ValueError(f"{'llm_fp4' if self.llm_fp4 else 'llm_fp8'} needs K a multiple of {need} ({why}): {name} is {K}")
             self.lm_head = None
             self.lm_head8, self.lm_head_s = quantize_rows_fp8_pow2(
                 (self.embed if tc.tie_word_embeddings else sd["lm_head.weight"]).to(device=device))
@@ -246,6 +309,9 @@ class EngineWeights:
             mats = [("qkv_w", qkv_w), ("o_w", sd[p + "self_attn.o_proj.weight"]), ("gu_w", gu_w), ("down_w", sd[p + "mlp.down_proj.weight"])]
             if self.llm_fp8:
                 self.layers.append(self._fp8_layer(sd, p, qkv_b, mats, device, dev))
+                continue
+            if self.llm_fp4:
+                self.layers.append(self._fp4_layer(sd, p, qkv_b, mats, device, dev))
                 continue
             flat = torch.empty(sum(m.numel() for _, m in mats), dtype=torch.bfloat16, device=device)
             layer = dict(ln1=dev(sd[p + "input_layernorm.weight"]), ln2=dev(sd[p + "post_attention_layernorm.weight"]), qkv_b=dev(qkv_b), flat=flat)
@@ -278,16 +344,40 @@ class EngineWeights:
             r0 += m.shape[0]
         return layer
 
+    @staticmethod
+    def _fp4_layer(sd, p, qkv_b, mats, device, dev):
+        """One layer in MXFP4: each matrix is quantised on `device` on its own, so at most one bf16 matrix exists beside the fp4 ones."""
+        n_w = sum(m.numel() for _, m in mats)
+        flat4 = torch.empty(n_w // 2, dtype=torch.uint8, device=device)
+        scale4 = torch.empty(n_w // 32, dtype=torch.uint8, device=device)
+        layer = dict(ln1=dev(sd[p + "input_layernorm.weight"]), ln2=dev(sd[p + "post_attention_layernorm.weight"]), qkv_b=dev(qkv_b),
+                     flat4=flat4, scale4=scale4)
+        off = 0
+        for name, m in mats:
+            codes, sc = quantize_blocks_mxfp4(m.to(device=device))
+            N, K = m.shape
+            layer[name + "4"] = flat4[off // 2:(off + N * K) // 2].view(N, K // 2)
+            layer[name + "_s4"] = scale4[off // 32:(off + N * K) // 32].view(N, K // 32)
+            layer[name + "4"].copy_(codes)
+            layer[name + "_s4"].copy_(sc)
+            del codes, sc
+            off += N * K
+        return layer
+
     def decode_bytes(self) -> int:
-        """Weight bytes one decode step streams (layers + final norm + lm_head): e4m3 codes and their row scales with `llm_fp8`."""
+        """Weight bytes one decode step streams (layers + final norm + lm_head): e4m3 codes and their row scales with `llm_fp8`, e2m1
+        codes and their block scales (and the e4m3 head) with `llm_fp4`."""
         n = self.final_norm.numel() * 2
-        if self.llm_fp8:
+        if self.llm_fp8 or self.llm_fp4:
             n += self.lm_head8.numel() + self.lm_head_s.numel() * 4
         else:
             n += self.lm_head.numel() * 2
         for l in self.layers:
-            n += sum(t.numel() * t.element_size() for k, t in l.items() if k not in ("flat", "flat8", "scale"))
+            n += sum(t.numel() * t.element_size() for k, t in l.items() if k not in ("flat", "flat8", "scale", "flat4", "scale4"))
         return n
+
+    def decode_weight_bytes(self) -> int:
+        return self.decode_bytes()
 
     def nbytes_llm_decode(self) -> int:
         return self.decode_bytes()
