@@ -11,13 +11,16 @@ __device__ __forceinline__ void am_better(float& best, int& bi, float x, int v) 
 // ---------------------------------------------------------------- top-k / top-p sampling (one workgroup)
 // HF order (generation/logits_process.py): repetition penalty -> temperature -> top-k (keep every score >= the k-th largest)
 // -> top-p (sort ascending, drop the tokens whose cumulative probability is <= 1 - top_p, always keep the largest) -> softmax ->
-// multinomial.  This kernel serves 1 < top_k < SF_CAP (ties at the threshold beyond the list's SF_CAP entries are cut by index);
-// top_k = 0 or >= SF_CAP goes to sample_nucleus_kernel below.
+// multinomial.  This kernel serves 1 < top_k < SF_CAP.  When more than SF_CAP scores reach the threshold (only possible through exact
+// ties of the k-th score) the list keeps the SF_CAP that ARRIVE first: the order the atomics land in, not the index order, so which of
+// the tied tokens survive is not deterministic.  top_k = 0 or >= SF_CAP goes to sample_nucleus_kernel below.
 #define SF_CAP 2048
 #define SF_THREADS 1024
 
-__device__ __forceinline__ unsigned sf_key(float x) {        // order-preserving float -> uint (larger score = larger key)
-  const unsigned u = __float_as_uint(x);
+// order-preserving float -> uint (larger score = larger key).  The zero is canonicalised first (-0.0f + 0.0f = +0.0f under
+// round-to-nearest): HF compares floats, for which -0.0 == +0.0 is a tie, and the two would get different keys otherwise.
+__device__ __forceinline__ unsigned sf_key(float x) {
+  const unsigned u = __float_as_uint(x + 0.0f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -268,6 +271,7 @@ __device__ __forceinline__ void sample_nucleus_body(const float* __restrict__ lo
       __syncthreads();
     }
     tau = sh_prefix;
+    __syncthreads();                                   // every thread has read sh_prefix before the mass descent below resets it
   }
   // ---- top-p threshold by mass among the keys >= tau: an entry survives iff the mass of the strictly larger ones is < top_p * Z
   if (top_p < 1.0f) {
