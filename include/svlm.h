@@ -352,6 +352,20 @@ int svlm_gemv_fp4(const void* x, const void* W4, int ldw, const void* w_scale, c
 /* dst[r, c] = bf16(code[r, c] * 2^e[r, c / 32]) for contiguous [rows, cols] matrices (cols a multiple of 32): the bf16 image W' of one
  * layer, which the prefill GEMMs read.  replaces: nothing (the reference has bf16 weights; this rebuilds them from the fp4 copy). */
 int svlm_dequant_fp4_bf16(const void* src4, const void* scale, void* dst, int rows, int cols, void* stream);
+/* svlm_gemm_bf16 / svlm_gemm_bf16_norm on W' = code * 2^e read straight from the MXFP4 codes (csrc/gemm_wfp4.hip): A stays bf16, W4 is
+ * N rows (2N for SVLM_ACT_SWIGLU, [gate; up]) of ldw BYTES (K / 2 of them codes), w_scale the e8m0 block scales of those rows in the
+ * same order ([rows, K / 32], contiguous, 2-B aligned).  The codes are staged at a quarter of the bytes of the bf16 image and converted
+ * (code * 2^e, exact in bf16) where a wave reads its MFMA fragment, so the MFMAs see the operands svlm_gemm_bf16 sees on
+ * svlm_dequant_fp4_bf16's output: with the same K per split (the dispatch restates svlm_gemm_bf16's plan) the outputs are bit-equal.
+ * K a multiple of 64, W4 16-B aligned, ldw a multiple of 16 and >= K / 2; N a multiple of 4 (8 with SVLM_ACT_SWIGLU or the norm);
+ * everything else as svlm_gemm_bf16 / svlm_gemm_bf16_norm.
+ * replaces: the prefill-row Linears of svlm_gemm_bf16 (qwen2/language_forward.py:80-82,161,201) for an fp4 language model, and the
+ * svlm_dequant_fp4_bf16 launch in front of each (`SvlmEngine(llm_fp4=True, prefill_fp4=True)`). */
+int svlm_gemm_wfp4(const void* A, int lda, const void* W4, int ldw, const void* w_scale, const void* bias, const void* residual, int ldr,
+                   void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, void* stream);
+int svlm_gemm_wfp4_norm(const void* A, int lda, const void* W4, int ldw, const void* w_scale, const void* bias, const void* residual,
+                        int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, const void* norm_w,
+                        const void* norm_b, float eps, void* XN, int ldxn, void* stream);
 
 /* ---- stream groups: lane-batched decode step (csrc/decode_batch.hip; stream_group.py).  B = 1..4 independent streams ("lanes") on
  * one GPU and ONE weight set take their decode step together: every kernel below reads each weight row once and multiplies it with the

@@ -85,6 +85,8 @@ SIGNATURES = {
     "svlm_dec_gate_up_fp4": (_i, [_p, _p, _f, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_gemv_fp4": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "svlm_dequant_fp4_bf16": (_i, [_p, _p, _p, _i, _i, _p]),
+    "svlm_gemm_wfp4": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "svlm_gemm_wfp4_norm": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _f, _p, _i, _p]),
     "svlm_decb_embed": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
     "svlm_decb_qkv": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "svlm_decb_gate_up": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p]),

@@ -36,6 +36,8 @@ FP8_LLM_OPS = ("dec_qkv_fp8", "dec_gate_up_fp8", "gemv_fp8", "dec_lm_head_fp8", 
 FP8_PREFILL_OPS = ("gemm_wfp8", "gemm_wfp8_norm")
 # ops entry points an llm_fp4 engine needs (csrc/decode_fp4.hip, and the fp8 head pair of csrc/decode_fp8.hip)
 FP4_LLM_OPS = ("dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4", "dequant_fp4", "gemv_fp8", "dec_lm_head_fp8")
+# ... and a prefill_fp4 engine on top of them (csrc/gemm_wfp4.hip)
+FP4_PREFILL_OPS = ("gemm_wfp4", "gemm_wfp4_norm")
 
 
 @dataclass
@@ -253,7 +255,7 @@ class SvlmEngine:
                  decode_chunk: Optional[int] = None, use_graph: Optional[bool] = None, kv_slack: float = 1.0, kv_page_tokens: int = 16,
                  decode_tail: Optional[bool] = None,
                  vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None,
-                 prefill_fp8: bool = False, llm_fp4: bool = False):
+                 prefill_fp8: bool = False, llm_fp4: bool = False, prefill_fp4: bool = False):
         """`share`: another engine of the same model whose WEIGHTS this one uses (language model, vision tower, embedding, lm_head,
         rope frequencies, fp8 vision images): `state_dict` is ignored and no weight tensor is copied; every per-stream buffer (sampling
         state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py).
@@ -264,11 +266,13 @@ class SvlmEngine:
         dequantisation launch, no scratch layer, nothing shared between the prefills of engines that share weights.
         `llm_fp4`: the layer matrices as OCP MXFP4 (e2m1 codes + one e8m0 scale per 32 weights), the lm_head e4m3 as with `llm_fp8`; the
         decode step streams them through the fp4 GEMVs (csrc/decode_fp4.hip), the prefill goes through the scratch layer, shared under
-        the same rule.  Not with `llm_fp8`, `prefill_fp8` or `decode_tail`."""
+        the same rule.  Not with `llm_fp8`, `prefill_fp8` or `decode_tail`.
+        `prefill_fp4` (with `llm_fp4`): the prefill GEMMs read the MXFP4 codes and block scales themselves (`gemm_wfp4`,
+        csrc/gemm_wfp4.hip), as `prefill_fp8` does for e4m3: no dequantisation launch, no scratch layer."""
         if share is not None:
             if (share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8
-                    or bool(prefill_fp8) != share.prefill_fp8 or bool(llm_fp4) != share.llm_fp4):
-                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, llm_fp4, prefill_fp8 and vit_fp8")
+                    or bool(prefill_fp8) != share.prefill_fp8 or bool(llm_fp4) != share.llm_fp4 or bool(prefill_fp4) != share.prefill_fp4):
+                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, llm_fp4, prefill_fp8, prefill_fp4 and vit_fp8")
             ops = share.ops if ops is None else ops
         if ops is None:
             from .ops import HipOps
@@ -314,6 +318,19 @@ class SvlmEngine:
                 raise ValueError(f"llm_fp4=True needs an ops backend with the fp4 entry points; {type(ops).__name__} lacks {missing}")
             if decode_tail or (decode_tail is None and os.environ.get("SVLM_DECODE_TAIL", "0") == "1"):
                 raise ValueError("llm_fp4=True cannot be combined with decode_tail=True (the persistent layer tail streams bf16 weights)")
+        # opt-in on top of llm_fp4: the prefill's four GEMMs per layer run on the e2m1 codes and their block scales (ops.gemm_wfp4*), which
+        # feed the MFMAs the operands the scratch layer would hold -- the same model W', without `dequant_fp4` and without the scratch layer
+        self.prefill_fp4 = bool(prefill_fp4)
+        if self.prefill_fp4:
+            if not self.llm_fp4:
+                raise ValueError("prefill_fp4=True needs llm_fp4=True (it is the prefill of the MXFP4 language-model weights)")
+            missing = [m for m in FP4_PREFILL_OPS if not hasattr(ops, m)]
+            if missing:
+                raise ValueError(f"prefill_fp4=True needs an ops backend with the weight-fp4 GEMMs; {type(ops).__name__} lacks {missing}")
+            tc_ = cfg.text
+            for name, K in (("hidden", tc_.hidden_size), ("q width", tc_.num_heads * tc_.head_dim), ("intermediate", tc_.intermediate_size)):
+                if K % 64:
+                    raise ValueError(f"prefill_fp4=True needs every GEMM K to be a multiple of 64 (one K-tile of the kernel): {name} is {K}")
         self._head_fp8 = self.llm_fp8 or self.llm_fp4          # the lm_head is e4m3 in both
         self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8, llm_fp4=self.llm_fp4)
         self._fp8_scratch = None           # llm_fp8 / llm_fp4: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
@@ -597,6 +614,10 @@ class SvlmEngine:
     # (tools/gemm_wfp8_vs_bf16.py, profiles/gemm_wfp8_vs_bf16.json): the direct GEMMs of a layer take 0.79x the scratch
     # path's time at M = 590 and 1.19x at M = 4096, where the conversion sits on a compute-bound loop and the dequantisation is amortised.
     PREFILL_FP8_MAX_ROWS = 1024
+    # prefill_fp4: the same threshold for the direct MXFP4 GEMMs.  It started as the fp8 value, unmeasured for fp4; measured since
+    # (tools/gemm_wfp4_vs_bf16.py, profiles/gemm_wfp4_vs_bf16.json): at the 7B widths the direct GEMMs of a layer take
+    # 0.76x the scratch path's time at M = 590 and 1.20x at M = 4096 (2B: 0.80x and 1.08x), so direct does not win at 4096 and the value stays.
+    PREFILL_FP4_MAX_ROWS = 1024
 
     def _prefill(self, c: KVPool, idx_dev, vis, T: int, L_before: int, head: bool = True):
         """Rows L_before .. L_before+T-1 through all layers (their K/V rows go to the pool); `head`: last-row logits."""
@@ -619,7 +640,20 @@ class SvlmEngine:
         o.rmsnorm(x, w.layers[0]["ln1"], tc.rms_eps, out=xn)
         # the four GEMMs of a layer on the e4m3 codes: no dequantisation, no scratch layer
         direct = self.prefill_fp8 and (self.PREFILL_FP8_MAX_ROWS is None or T <= self.PREFILL_FP8_MAX_ROWS)
+        # ... or on the MXFP4 codes and block scales
+        direct4 = self.prefill_fp4 and (self.PREFILL_FP4_MAX_ROWS is None or T <= self.PREFILL_FP4_MAX_ROWS)
         for li, lw in enumerate(w.layers):
+            if direct4:
+                o.gemm_wfp4(xn, lw["qkv_w4"], lw["qkv_w_s4"], bias=lw["qkv_b"], out=qkv)
+                o.prefill_attn(qkv[:, :qd], c.pool, li, c.slot_of_dev, self.rope_cs, attn, T, L, tc.num_heads, scale,
+                               k_new=qkv[:, qd:qd + kd], v_new=qkv[:, qd + kd:], lin=lin)
+                o.gemm_wfp4_norm(attn, lw["o_w4"], lw["o_w_s4"], lw["ln2"], tc.rms_eps, x, xn, residual=x)
+                o.gemm_wfp4(xn, lw["gu_w4"], lw["gu_w_s4"], out=hm, act=ACT_SWIGLU)          # H % 64 == 0 (checked at construction)
+                if li + 1 < n_layers:
+                    o.gemm_wfp4_norm(hm, lw["down_w4"], lw["down_w_s4"], w.layers[li + 1]["ln1"], tc.rms_eps, x, xn, residual=x)
+                else:
+                    o.gemm_wfp4(hm, lw["down_w4"], lw["down_w_s4"], residual=x, out=x)
+                continue
             if direct:
                 o.gemm_wfp8(xn, lw["qkv_w8"], lw["qkv_w_s"], bias=lw["qkv_b"], out=qkv)
                 o.prefill_attn(qkv[:, :qd], c.pool, li, c.slot_of_dev, self.rope_cs, attn, T, L, tc.num_heads, scale,

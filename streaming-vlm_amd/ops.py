@@ -131,8 +131,8 @@ class HipOps:
         return out, out_norm
 
     def last_gemm_plan(self):
-        """What the last gemm / gemm_norm / gemm_fp8 / gemm_wfp8 call of this process launched (`fp8`: 0 bf16, 1 fp8 x fp8, 2 weight-fp8);
-        diagnostic library only."""
+        """What the last gemm / gemm_norm / gemm_fp8 / gemm_wfp8 call of this process launched (`fp8`: 0 bf16, 1 fp8 x fp8, 2 weight-fp8,
+        3 weight-fp4: gemm_wfp4); diagnostic library only."""
         fn = getattr(self.lib, "svlm_diag_last_gemm_plan", None)
         if fn is None:
             raise _lib.SvlmError("last_gemm_plan: the product library keeps no plan note; bind HipOps to the diagnostic library")
@@ -1042,4 +1042,56 @@ class HipOps:
         self._check(self.lib.svlm_gemm_wfp8_norm(_ptr(A), A.stride(0), _ptr(W8), W8.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), ldr,
                                            _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _ptr(norm_w), _ptr(norm_b),
                                            float(eps), _ptr(out_norm), out_norm.stride(0), _stream()), "svlm_gemm_wfp8_norm")
+        return out, out_norm
+
+    # ------------------------------------------------------------------ prefill GEMMs on the MXFP4 weights (csrc/gemm_wfp4.hip)
+    def gemm_wfp4(self, A, W4, w_scale, bias=None, residual=None, out=None, act=ACT_NONE):
+        """`gemm` on W' = code * 2^e read straight from the e2m1 codes and their e8m0 block scales (no bf16 image of W); K % 64 == 0."""
+        _req(A, BF16, "gemm_wfp4.A", 2)
+        N, K = self._req_fp4(W4, w_scale, "gemm_wfp4")
+        M, K2 = A.shape
+        if K != K2 or K % 64:
+            raise _lib.SvlmError(f"gemm_wfp4: A is {tuple(A.shape)} but W4 holds {N} x {K} codes; K must be a multiple of 64")
+        if act == ACT_SWIGLU:          # W4 = [gate rows; up rows]: the output has half as many columns
+            if N % 2 or residual is not None or (bias is not None and bias.numel() != N):
+                raise _lib.SvlmError("gemm_wfp4: ACT_SWIGLU takes W4 = [gate; up] (even row count), bias = [gate; up], no residual")
+            N //= 2
+        if out is None:
+            out = torch.empty((M, N), dtype=BF16, device=A.device)
+        _req(out, BF16, "gemm_wfp4.out", 2)
+        if tuple(out.shape) != (M, N):
+            raise _lib.SvlmError(f"gemm_wfp4: out shape {tuple(out.shape)} != {(M, N)}")
+        if bias is not None:
+            _req(bias, BF16, "gemm_wfp4.bias", 1)
+            assert bias.numel() == (2 * N if act == ACT_SWIGLU else N)
+        ldr = 0
+        if residual is not None:
+            _req(residual, BF16, "gemm_wfp4.residual", 2)
+            assert tuple(residual.shape) == (M, N)
+            ldr = residual.stride(0)
+        ws = self._ws(A.device)
+        self._check(self.lib.svlm_gemm_wfp4(_ptr(A), A.stride(0), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), ldr,
+                                      _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _stream()), "svlm_gemm_wfp4")
+        return out
+
+    def gemm_wfp4_norm(self, A, W4, w_scale, norm_w, eps, out, out_norm, bias=None, residual=None, act=ACT_NONE, norm_b=None):
+        """`gemm_norm` on W' = code * 2^e read straight from the codes."""
+        _req(A, BF16, "gemm_wfp4_norm.A", 2); _req(out, BF16, "gemm_wfp4_norm.out", 2)
+        _req(out_norm, BF16, "gemm_wfp4_norm.out_norm", 2); _req(norm_w, BF16, "gemm_wfp4_norm.norm_w", 1)
+        N, K = self._req_fp4(W4, w_scale, "gemm_wfp4_norm")
+        M = A.shape[0]
+        if A.shape[1] != K or K % 64:
+            raise _lib.SvlmError(f"gemm_wfp4_norm: A is {tuple(A.shape)} but W4 holds {N} x {K} codes; K must be a multiple of 64")
+        assert tuple(out.shape) == (M, N) == tuple(out_norm.shape) and norm_w.numel() == N
+        ldr = 0
+        if residual is not None:
+            _req(residual, BF16, "gemm_wfp4_norm.residual", 2)
+            assert tuple(residual.shape) == (M, N)
+            ldr = residual.stride(0)
+        if bias is not None:
+            _req(bias, BF16, "gemm_wfp4_norm.bias", 1)
+        ws = self._ws(A.device)
+        self._check(self.lib.svlm_gemm_wfp4_norm(_ptr(A), A.stride(0), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), ldr,
+                                           _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _ptr(norm_w), _ptr(norm_b),
+                                           float(eps), _ptr(out_norm), out_norm.stride(0), _stream()), "svlm_gemm_wfp4_norm")
         return out, out_norm

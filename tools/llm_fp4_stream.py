@@ -1,13 +1,18 @@
 """The opt-in MXFP4 language model (SvlmEngine(llm_fp4=True)) against the bf16 default and the fp8 engine on the bench streams.
 
-    python tools/llm_fp4_stream.py [2b|7b ...] [--steps K] [--warmup W] [--repeats R] [--out DIR] [--no-kernels]
+    python tools/llm_fp4_stream.py [2b|7b ...] [--steps K] [--warmup W] [--repeats R] [--out DIR] [--no-kernels] [--prefill-fp4]
 
 Per model ONE child process builds the bf16, the fp8 (scratch-layer prefill) and the fp4 model and runs their streams in alternation
 (tools/llm_fp8_stream.py:stream_run: the window is filled first, then K chunks are timed as bench.py does), `--repeats` times each.  The
 record (profiles/llm_fp4_<model>.json with --out) holds every pass and per form the median and the spread of the repeats of frames/s, ms
 per chunk, prefill ms per chunk and microseconds per decode step, the decode weight bytes, and the fp4 - fp8 decode-step difference
 against that spread.  A second child times the four weight-streaming layer kernels in bf16, fp8 and fp4 at the model's shapes over 8
-layers of distinct weights, cold (512 MiB written between replays), bytes being each form's own weight bytes (+ scales, activations)."""
+layers of distinct weights, cold (512 MiB written between replays), bytes being each form's own weight bytes (+ scales, activations).
+
+`--prefill-fp4`: the alternating set becomes bf16, fp8 with the direct prefill (prefill_fp8=True), fp4 with the scratch-layer prefill and
+fp4 with the direct prefill (prefill_fp4=True: the prefill GEMMs read the MXFP4 weights, csrc/gemm_wfp4.hip); no kernel child; the
+record goes to profiles/llm_fp4_prefill_<model>.json and its summary holds the direct - scratch prefill difference per chunk against
+the largest repeat spread."""
 import argparse
 import json
 import os
@@ -22,6 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import llm_fp8_stream as F8          # noqa: E402  (stream_run, the stream geometry)
 
 FORMS = {"bf16": {}, "fp8": dict(llm_fp8=True), "fp4": dict(llm_fp4=True)}
+PREFILL_FORMS = {"bf16": {}, "fp8_direct": dict(llm_fp8=True, prefill_fp8=True), "fp4": dict(llm_fp4=True),
+                 "fp4_direct": dict(llm_fp4=True, prefill_fp4=True)}
 
 
 def build(model_name, **kw):
@@ -37,13 +44,14 @@ def build(model_name, **kw):
     return S.StreamingQwen2VL(cfg, random_state_dict(cfg, 0, dev), dev, max_len=max_len, max_new_tokens=F8.NEW, **kw)
 
 
-def stream_runs(model_name, steps, warmup, repeats):
+def stream_runs(model_name, steps, warmup, repeats, prefill_fp4=False):
+    FORMS = PREFILL_FORMS if prefill_fp4 else globals()["FORMS"]
     models = {name: build(model_name, **kw) for name, kw in FORMS.items()}
     passes = {k: [] for k in FORMS}
     for r in range(repeats):
         for name in FORMS:
-            rec, _ = F8.stream_run(model_name, name == "fp8", steps, warmup, model=models[name])
-            rec.update(form=name, repeat=r, llm_fp4=name == "fp4",
+            rec, _ = F8.stream_run(model_name, name.startswith("fp8"), steps, warmup, model=models[name])
+            rec.update(form=name, repeat=r, llm_fp4=name.startswith("fp4"), prefill_fp4=name == "fp4_direct", prefill_fp8=name == "fp8_direct",
                        decode_us_per_step=round(1e3 * rec["decode_ms_per_chunk"] / max(rec["decode_steps_per_chunk"], 1), 2))
             del rec["build_seconds"]
             passes[name].append(rec)
@@ -54,6 +62,15 @@ def stream_runs(model_name, steps, warmup, repeats):
             v = [p[key] for p in ps]
             summ[f"{name}.{key}"] = {"median": round(statistics.median(v), 3), "spread": round(max(v) - min(v), 3)}
         summ[f"{name}.decode_weight_bytes"] = ps[0]["decode_weight_bytes"]
+    if prefill_fp4:
+        pf = lambda n: summ[f"{n}.prefill_ms_per_chunk"]
+        summ["run"] = "fp4_prefill_summary"
+        summ["prefill_ms_direct_minus_scratch"] = round(pf("fp4_direct")["median"] - pf("fp4")["median"], 3)
+        summ["prefill_ms_direct_minus_bf16"] = round(pf("fp4_direct")["median"] - pf("bf16")["median"], 3)
+        summ["prefill_ms_direct_minus_fp8_direct"] = round(pf("fp4_direct")["median"] - pf("fp8_direct")["median"], 3)
+        summ["prefill_ms_repeat_spread"] = max(pf(n)["spread"] for n in FORMS)
+        summ["scratch_layer_allocated"] = {n: models[n]._svlm_engine._fp8_scratch is not None for n in FORMS}
+        return lines + [summ]
     du = lambda n: summ[f"{n}.decode_us_per_step"]
     summ["decode_us_fp4_minus_fp8"] = round(du("fp4")["median"] - du("fp8")["median"], 2)
     summ["decode_us_fp4_minus_bf16"] = round(du("fp4")["median"] - du("bf16")["median"], 2)
@@ -134,18 +151,20 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="passes per form (their spread is the noise)")
     ap.add_argument("--out", default=None, help="directory: one llm_fp4_<model>.json per model (all of its lines)")
     ap.add_argument("--no-kernels", action="store_true", help="skip the per-kernel child")
+    ap.add_argument("--prefill-fp4", action="store_true", help="bf16, direct fp8, scratch fp4 and direct fp4 (prefill_fp4=True) streams")
     ap.add_argument("--child", nargs=2, metavar=("MODEL", "RUN"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         m, run = args.child
-        for line in ([kernel_run(m)] if run == "kernels" else stream_runs(m, args.steps, args.warmup, args.repeats)):
+        for line in ([kernel_run(m)] if run == "kernels" else stream_runs(m, args.steps, args.warmup, args.repeats, args.prefill_fp4)):
             print(json.dumps(line), flush=True)
         return
     for m in args.models:
         lines = []
-        for run in ("streams",) + (() if args.no_kernels else ("kernels",)):
+        for run in ("streams",) + (() if args.no_kernels or args.prefill_fp4 else ("kernels",)):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--repeats",
-                                str(args.repeats), "--child", m, run], capture_output=True, text=True)
+                                str(args.repeats), *(["--prefill-fp4"] if args.prefill_fp4 else []), "--child", m, run],
+                               capture_output=True, text=True)
             if p.returncode != 0:
                 sys.stderr.write(p.stderr[-4000:])
                 raise SystemExit(f"{m} {run}: child exited with {p.returncode}")
@@ -155,7 +174,7 @@ def main():
             lines += new
         if args.out:
             os.makedirs(args.out, exist_ok=True)
-            with open(os.path.join(args.out, f"llm_fp4_{m}.json"), "w") as f:
+            with open(os.path.join(args.out, f"llm_fp4_prefill_{m}.json" if args.prefill_fp4 else f"llm_fp4_{m}.json"), "w") as f:
                 json.dump(lines, f, indent=1)
 
 
