@@ -433,6 +433,25 @@ int svlm_decb_gemv_fp8(const void* lanes, int B, const void* x, int ldx, const v
 int svlm_decb_lm_head_fp8(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W8, int ldw,
                           const float* w_scale, float* logits, int ldl, const int* suppress, void* ws, int V, int K, void* stream);
 
+/* ---- stream groups on MXFP4 language-model weights (csrc/decode_batch_fp4.hip): the lane-batched twins of the single-row fp4 entries
+ * above.  W4: e2m1 codes, two per byte, at a row stride of ldw BYTES (ldw >= K / 2, a multiple of 16); w_scale: the e8m0 bytes, K / 32
+ * per row, contiguous.  Per (lane, output row) every output is BITWISE what the single-row fp4 entry computes for the lane alone; each
+ * 16-code half block is converted to fp32 (block scale included) once for all B lanes.  Same lane table, same skipping of a lane that
+ * is not live.  B in 1..4, K a multiple of 32, ldx >= K a multiple of 8; K <= 8192 and B * K * 2 <= 65536 - 256 for the two entries
+ * that stage the normalised rows in LDS.  There is no fp4 head: the lm_head of an fp4 engine is e4m3, so svlm_decb_lm_head[_sample]_fp8,
+ * svlm_decb_embed and the finish entries serve unchanged.
+ * replaces: qwen2/language_forward.py:183,80-82 + generate/streaming_cache.py:72-73 (as svlm_dec_qkv_fp4).  head_dim 128. */
+int svlm_decb_qkv_fp4(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W4, int ldw,
+                      const void* w_scale, const void* bias, void* q_out, int ldq, int layer, int K, int qd, int kd, int D, void* stream);
+/* replaces: qwen2/language_forward.py:200-201 (Qwen2MLP gate/up + SwiGLU, as svlm_dec_gate_up_fp4). */
+int svlm_decb_gate_up_fp4(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W4, int ldw,
+                          const void* w_scale, void* h, int ldh, int I, int K, void* stream);
+/* svlm_gemv_fp4 with residual for B lanes: y[b] = bf16(bf16(W' x[b]) + residual[b]); y may be residual.  Every shape takes the form
+ * (rows per wave, K split over the waves) the single-row entry takes.
+ * replaces: o_proj / down_proj at T = 1 (qwen2/language_forward.py:161,201). */
+int svlm_decb_gemv_fp4(const void* lanes, int B, const void* x, int ldx, const void* W4, int ldw, const void* w_scale,
+                       const void* residual, int ldr, void* y, int ldy, int N, int K, void* stream);
+
 /* ---- stream groups: per-lane sampling (stream_group.py, StreamGroup(sampling=True)).  The reference's default token choice
  * (do_sample=True at inference.py:446 with HF's warpers) for the lanes of a group: every lane has its own temperature / top-k / top-p and
  * its own Philox seed, in a table of B svlm_lane_sample records parallel to the lane table (record b belongs to lane b).  `mode` is chosen

@@ -98,6 +98,9 @@ SIGNATURES = {
     "svlm_decb_gate_up_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p]),
     "svlm_decb_gemv_fp8": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),
     "svlm_decb_lm_head_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p]),
+    "svlm_decb_qkv_fp4": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "svlm_decb_gate_up_fp4": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p]),
+    "svlm_decb_gemv_fp4": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),
     "svlm_decb_lm_head_sample": (_i, [_p, _p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_decb_lm_head_sample_fp8": (_i, [_p, _p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_decb_sample_finish": (_i, [_p, _p, _i, _p, _i, _p, _p, _i, _i, _p]),

@@ -849,6 +849,32 @@ class HipOps:
                                                     _ptr(w_scale), _ptr(logits), ldl, _ptr(suppress), _ptr(ws), V, K, _stream()),
               "svlm_decb_lm_head_sample_fp8")
 
+    # the layer kernels on MXFP4 weights (csrc/decode_batch_fp4.hip): (W4, w_scale) = e2m1 codes + e8m0 block scales where W stands.
+    # There is no fp4 head: an fp4 engine's lm_head is e4m3 and goes through decb_lm_head[_sample]_fp8
+    def decb_qkv_fp4(self, lanes, B, x, ln_w, eps, W4, w_scale, bias, q_out, layer, qd, kd, D, n_layers):
+        self._lanes(lanes, B, "decb_qkv_fp4"); _req(ln_w, BF16, "decb_qkv_fp4.ln_w", 1); _req(bias, BF16, "decb_qkv_fp4.bias", 1)
+        N, K = self._req_fp4(W4, w_scale, "decb_qkv_fp4")
+        assert N == qd + 2 * kd == bias.numel() and ln_w.numel() == K and 0 <= layer < n_layers
+        ldx, ldq = self._rows(x, B, K, "decb_qkv_fp4.x"), self._rows(q_out, B, qd, "decb_qkv_fp4.q_out")
+        self._check(self.lib.svlm_decb_qkv_fp4(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias),
+                                         _ptr(q_out), ldq, int(layer), K, qd, kd, D, _stream()), "svlm_decb_qkv_fp4")
+
+    def decb_gate_up_fp4(self, lanes, B, x, ln_w, eps, W4, w_scale, h):
+        self._lanes(lanes, B, "decb_gate_up_fp4"); _req(ln_w, BF16, "decb_gate_up_fp4.ln_w", 1)
+        N, K = self._req_fp4(W4, w_scale, "decb_gate_up_fp4")
+        assert N % 2 == 0 and ln_w.numel() == K
+        ldx, ldh = self._rows(x, B, K, "decb_gate_up_fp4.x"), self._rows(h, B, N // 2, "decb_gate_up_fp4.h")
+        self._check(self.lib.svlm_decb_gate_up_fp4(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(h),
+                                             ldh, N // 2, K, _stream()), "svlm_decb_gate_up_fp4")
+
+    def decb_gemv_fp4(self, lanes, B, x, W4, w_scale, residual, out):
+        self._lanes(lanes, B, "decb_gemv_fp4")
+        N, K = self._req_fp4(W4, w_scale, "decb_gemv_fp4")
+        ldx, ldr = self._rows(x, B, K, "decb_gemv_fp4.x"), self._rows(residual, B, N, "decb_gemv_fp4.residual")
+        ldy = self._rows(out, B, N, "decb_gemv_fp4.out")
+        self._check(self.lib.svlm_decb_gemv_fp4(_ptr(lanes), B, _ptr(x), ldx, _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(residual), ldr, _ptr(out),
+                                          ldy, N, K, _stream()), "svlm_decb_gemv_fp4")
+
     # ------------------------------------------------------------------ fp8 language-model weights (csrc/decode_fp8.hip)
     @staticmethod
     def _req_fp8(W8, scale, name):

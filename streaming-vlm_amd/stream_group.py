@@ -3,6 +3,9 @@ the lane-batched kernels of csrc/decode_batch.hip -- each weight byte is read on
 An `llm_fp8=True` engine takes the same steps through the e4m3 twins of csrc/decode_batch_fp8.hip: half the weight bytes, read once
 for B tokens, and each weight converted to fp32 once for all B lanes.  Its prefill stays per stream and dequantises layer by layer
 into ONE bf16 scratch layer that all lanes share (a group pays that dequantisation once per lane and chunk).
+An `llm_fp4=True` engine takes them through the MXFP4 twins of csrc/decode_batch_fp4.hip (e2m1 codes + e8m0 block scales, a quarter of
+the bf16 bytes, each half block converted once for all B lanes) and the e4m3 head; with `prefill_fp4=True` every lane's prefill reads
+the codes directly, otherwise (or for a pass above `PREFILL_FP4_MAX_ROWS`) the lanes share the one scratch layer as fp8 lanes do.
 
 A lane is an `SvlmEngine` that shares the group engine's weights (`SvlmEngine(share=...)`; lane 0 IS the group engine) and owns
 everything a stream owns: KV pool, positions, rope table, sampling state, eviction history.  `StreamGroup.generate` runs
@@ -21,7 +24,8 @@ engine with the same generator seed (a seed mixes in how many sampled calls the 
 
 Opt-in; nothing here is reached by the single-stream path.  Refused with a ValueError instead of silently falling back:
 `decode_tail=True` engines, an `llm_fp8=True` engine whose ops backend lacks the batched fp8 entry points (with `sampling=True` also the
-fp8 sampling head), `do_sample=True` with anything but `top_k == 1` unless the group was built with `sampling=True`, `force_tokens`,
+fp8 sampling head), an `llm_fp4=True` engine whose ops backend lacks the batched fp4 entry points or the batched fp8 head (with
+`sampling=True` also the fp8 sampling head), `do_sample=True` with anything but `top_k == 1` unless the group was built with `sampling=True`, `force_tokens`,
 `keep_logits`.
 The look-ahead ViT (`next_vision`) is DECLINED: a group runs strict-causal, every chunk's vision tower runs inside its own
 `generate_begin`.
@@ -47,6 +51,8 @@ MAX_LANES = 4
 DEFAULT_LANES = 3
 # ops entry points a group on an llm_fp8 engine needs (csrc/decode_batch_fp8.hip)
 FP8_GROUP_OPS = ("decb_qkv_fp8", "decb_gate_up_fp8", "decb_gemv_fp8", "decb_lm_head_fp8")
+# ... and on an llm_fp4 engine (csrc/decode_batch_fp4.hip; the lm_head of an fp4 engine is e4m3)
+FP4_GROUP_OPS = ("decb_qkv_fp4", "decb_gate_up_fp4", "decb_gemv_fp4", "decb_lm_head_fp8")
 
 
 def check_request(req: dict, sampling: bool = False) -> dict:
@@ -172,7 +178,13 @@ class StreamGroup:
                 raise ValueError(f"stream group: sampling=True on an llm_fp8=True engine needs an ops backend with the lane-batched fp8 "
                                  f"sampling head; {type(engine.ops).__name__} lacks decb_lm_head_sample_fp8")
         if getattr(engine, "llm_fp4", False):
-            raise ValueError("stream group: llm_fp4=True engines are not supported (there are no lane-batched fp4 decode kernels)")
+            missing = [m for m in FP4_GROUP_OPS if not hasattr(getattr(engine, "ops", None), m)]
+            if missing:
+                raise ValueError(f"stream group: an llm_fp4=True engine needs an ops backend with the lane-batched fp4 entry points and the "
+                                 f"lane-batched fp8 head; {type(getattr(engine, 'ops', None)).__name__} lacks {missing}")
+            if sampling and not hasattr(engine.ops, "decb_lm_head_sample_fp8"):
+                raise ValueError(f"stream group: sampling=True on an llm_fp4=True engine needs an ops backend with the lane-batched fp8 "
+                                 f"sampling head; {type(engine.ops).__name__} lacks decb_lm_head_sample_fp8")
         if getattr(engine, "decode_tail", False):
             raise ValueError("stream group: decode_tail=True engines are not supported (the persistent layer tail is single-row)")
         self.engine = engine
@@ -183,7 +195,7 @@ class StreamGroup:
             SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
                        use_graph=engine.use_graph, kv_slack=engine.kv_slack, kv_page_tokens=engine.kv_page_tokens, decode_tail=False,
                        vit_fp8=engine.vit_fp8, linear_planes=engine.linear_planes, llm_fp8=engine.llm_fp8, share=engine,
-                       prefill_fp8=engine.prefill_fp8)
+                       prefill_fp8=engine.prefill_fp8, llm_fp4=engine.llm_fp4, prefill_fp4=engine.prefill_fp4)
             for _ in range(self.n_lanes - 1)]
         for ln in self.lanes[1:]:
             ln.default_top_k, ln.default_top_p, ln.eos_dev = engine.default_top_k, engine.default_top_p, engine.eos_dev
@@ -249,14 +261,15 @@ class StreamGroup:
         """The head and the token feedback.  `sampled`: some lane of the batch draws its token -- the head adds the Gumbel noise where a
         lane's record asks for it and the finish branches on each lane's mode; an all-greedy batch keeps the greedy pair."""
         e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
+        head_fp8 = e.llm_fp8 or getattr(e, "llm_fp4", False)         # the lm_head is e4m3 in both
         if not sampled:
-            if e.llm_fp8:
+            if head_fp8:
                 o.decb_lm_head_fp8(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, self.suppress, self.ws)
             else:
                 o.decb_lm_head(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
             o.decb_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
             return
-        if e.llm_fp8:
+        if head_fp8:
             o.decb_lm_head_sample_fp8(tab, self.samples, B, self.x, w.final_norm, tc.rms_eps, w.lm_head8, w.lm_head_s, self.logits, self.suppress,
                                       self.ws)
         else:
@@ -273,6 +286,10 @@ class StreamGroup:
         o.decb_embed(tab, B, w.embed, self.x)
         if e.llm_fp8:
             self._layers_fp8(act, tab, B, scale)
+            self._head(tab, B, sampled)
+            return
+        if getattr(e, "llm_fp4", False):
+            self._layers_fp4(act, tab, B, scale)
             self._head(tab, B, sampled)
             return
         for li, lw in enumerate(w.layers):
@@ -298,6 +315,20 @@ class StreamGroup:
             o.decb_gemv_fp8(tab, B, self.attn, lw["o_w8"], lw["o_w_s"], self.x, self.x)
             o.decb_gate_up_fp8(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w8"], lw["gu_w_s"], self.h)
             o.decb_gemv_fp8(tab, B, self.h, lw["down_w8"], lw["down_w_s"], self.x, self.x)
+
+    def _layers_fp4(self, act, tab, B, scale):
+        """The layers of `_step_launch` on MXFP4 weights: `_layers_fp8` with the weight-streaming kernels replaced by their fp4 twins
+        (csrc/decode_batch_fp4.hip) on the e2m1 codes and e8m0 block scales."""
+        e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
+        qd, kd, nl = e.qd, e.kd, len(w.layers)
+        for li, lw in enumerate(w.layers):
+            o.decb_qkv_fp4(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w4"], lw["qkv_w_s4"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
+            for j, (lane, c) in enumerate(act):
+                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
+                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            o.decb_gemv_fp4(tab, B, self.attn, lw["o_w4"], lw["o_w_s4"], self.x, self.x)
+            o.decb_gate_up_fp4(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w4"], lw["gu_w_s4"], self.h)
+            o.decb_gemv_fp4(tab, B, self.h, lw["down_w4"], lw["down_w_s4"], self.x, self.x)
 
     def _step(self, idx, act, sampled: bool = False):
         if not self.use_graph:

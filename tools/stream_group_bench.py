@@ -17,6 +17,14 @@ is read against the bf16 group and the solo fp8 stream of ONE run, never against
 (csrc/gemm_wfp8.hip), no dequantisation into a scratch layer -- and the groups of the scratch-layer fp8 model ("group_fp8_scratch") run in
 the same process beside the bf16 groups, so direct fp8, scratch fp8 and bf16 groups are all of ONE run.
 
+`--llm-fp4`: the model is built with llm_fp4=True (MXFP4 language-model weights, e4m3 head) and takes the same passes through the
+lane-batched fp4 kernels (csrc/decode_batch_fp4.hip); the fp8 groups ("group_fp8") and the bf16 groups ("group_bf16") of the same weights run
+in the same process, and per lane count the fp4 decode step is read against the fp8 step of the same run, with the spread of the replay
+rounds of both next to it.
+
+`--prefill-fp4` (implies --llm-fp4): the fp4 model is built with prefill_fp4=True (csrc/gemm_wfp4.hip) and the fp8 model it is read
+against with prefill_fp8=True: direct fp4, direct fp8 and bf16 groups of ONE run.
+
 `--sample T[,K[,P]]` (may be given more than once): after the greedy passes, the same passes with every stream drawing its tokens
 (do_sample=True at temperature T, top_k K -- 0 = off, the default -- and top_p P, a generator seed per stream) through
 `StreamGroup(sampling=True)`, and the solo sampled stream of the same run; per setting and B the decode step is read against the greedy
@@ -30,6 +38,8 @@ Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- pyth
     python tools/stream_group_bench.py --llm-fp8                                      (writes profiles/stream_group_fp8_2b.json)
     python tools/stream_group_bench.py --llm-fp8 --model 7b --fps 2 --window 4096     (writes profiles/stream_group_fp8_7b.json)
     python tools/stream_group_bench.py --prefill-fp8 [--model 7b --fps 2 --window 4096]  (writes profiles/stream_group_prefill_fp8_<model>.json)
+    python tools/stream_group_bench.py --llm-fp4                                      (writes profiles/stream_group_fp4_2b.json)
+    python tools/stream_group_bench.py --prefill-fp4 [--model 7b --fps 2 --window 4096]  (writes profiles/stream_group_prefill_fp4_<model>.json)
     python tools/stream_group_bench.py --sample 0.9 --sample 0.9,50,1.0               (writes profiles/stream_group_sampling_2b.json)
 """
 import argparse
@@ -53,12 +63,13 @@ from streaming_vlm_amd.weights import random_state_dict  # noqa: E402
 
 def weight_bytes(kernel, tc):
     """Weight bytes one launch of a lane-batched (decb_*) kernel streams, from its name: e4m3 codes + fp32 row scales for the fp8 twins,
-    bf16 otherwise.  The residual GEMV that splits K over the waves (down_proj) is told from the plain one (o_proj) by its name / KW."""
+    e2m1 codes + e8m0 block scales for the fp4 twins, bf16 otherwise.  The residual GEMV that splits K over the waves (down_proj) is told from the plain one (o_proj) by its name / KW."""
     import re
-    if "decb_" not in kernel or "embed" in kernel or "argmax" in kernel:
+    single4 = "decb_" not in kernel and any(k in kernel for k in ("dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4"))     # the single-row fp4 twins
+    if ("decb_" not in kernel and not single4) or "embed" in kernel or "argmax" in kernel:
         return 0
     H, I, qd, kd = tc.hidden_size, tc.intermediate_size, tc.num_heads * tc.head_dim, tc.num_kv_heads * tc.head_dim
-    fp8 = "_fp8" in kernel
+    fp8, fp4 = "_fp8" in kernel, "_fp4" in kernel
     if "qkv" in kernel:
         n, k = qd + 2 * kd, H
     elif "gate_up" in kernel:
@@ -66,11 +77,14 @@ def weight_bytes(kernel, tc):
     elif "lm_head" in kernel:
         n, k = tc.vocab_size, H
     elif "gemv" in kernel:
-        m = re.search(r"<\s*\d+\s*,\s*\d+\s*,\s*(\d+)\s*,", kernel)
-        split = "ksplit" in kernel or (fp8 and m is not None and m.group(1) == "4")
+        # KW is the third template argument of the lane-batched GEMVs (NB, ROWS, KW, PRE), the second of gemv_fp4_kernel (ROWS, KW, PRE)
+        m = re.search(r"<\s*\d+\s*,\s*(\d+)\s*,\s*\d+\s*>", kernel) if single4 else re.search(r"<\s*\d+\s*,\s*\d+\s*,\s*(\d+)\s*,", kernel)
+        split = "ksplit" in kernel or ((fp8 or fp4) and m is not None and m.group(1) == "4")
         n, k = (H, I) if split else (H, qd)
     else:
         return 0
+    if fp4:
+        return n * k // 2 + n * k // 32
     return n * k + 4 * n if fp8 else 2 * n * k
 
 
@@ -80,12 +94,14 @@ def kernel_stats(path, cfg):
     for r in csv.DictReader(open(path)):
         name = r.get("Name") or r.get("KernelName") or ""
         if any(k in name for k in ("decb_", "dec_qkv_kernel", "dec_gate_up_kernel", "dec_lm_head_kernel", "gemv_bf16", "argmax_finish", "decode_attn",
-                                   "dec_qkv_fp8", "dec_gate_up_fp8", "dec_lm_head_fp8", "gemv_fp8", "dequant_fp8")):
+                                   "dec_qkv_fp8", "dec_gate_up_fp8", "dec_lm_head_fp8", "gemv_fp8", "dequant_fp8",
+                                   "dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4", "dequant_fp4")):
             rec = rows[name[:120]] = dict(calls=int(r["Calls"]), avg_us=float(r["AverageNs"]) / 1e3)
             nbytes = weight_bytes(name, cfg.text)
             if nbytes:
                 rec["weight_bytes"] = nbytes
                 rec["weight_tb_per_s"] = nbytes / (rec["avg_us"] * 1e-6) / 1e12
+                rec["weight_gb_per_s"] = 1e3 * rec["weight_tb_per_s"]
     return rows
 
 
@@ -103,6 +119,9 @@ def main():
     ap.add_argument("--llm-fp8", action="store_true", help="e4m3 language-model weights: fp8 solo + fp8 groups, and the bf16 groups of the same run")
     ap.add_argument("--prefill-fp8", action="store_true", help="--llm-fp8 with the prefill on the e4m3 weights (prefill_fp8=True); the scratch-layer "
                                                                "fp8 groups and the bf16 groups run in the same process")
+    ap.add_argument("--llm-fp4", action="store_true", help="MXFP4 language-model weights: fp4 solo + fp4 groups, and the fp8 and bf16 groups of the same run")
+    ap.add_argument("--prefill-fp4", action="store_true", help="--llm-fp4 with the prefill on the MXFP4 weights (prefill_fp4=True); the fp8 groups it is "
+                                                               "read against get prefill_fp8=True")
     ap.add_argument("--sample", action="append", default=[], metavar="T[,K[,P]]",
                     help="also run solo and groups with every stream sampling at temperature T, top_k K (0 = off) and top_p P")
     ap.add_argument("--kernels-only", action="store_true", help="one short pass per B and nothing else (for a rocprofv3 --kernel-trace run)")
@@ -112,6 +131,10 @@ def main():
     ap.add_argument("--out", default=None, help="record file; --llm-fp8 timed runs default to profiles/stream_group_fp8_<model>.json")
     args = ap.parse_args()
     args.llm_fp8 = args.llm_fp8 or args.prefill_fp8
+    args.llm_fp4 = args.llm_fp4 or args.prefill_fp4
+    if args.llm_fp4 and args.llm_fp8:
+        ap.error("--llm-fp4 / --prefill-fp4 and --llm-fp8 / --prefill-fp8 are two formats of the same matrices: one run, one of them "
+                 "(an fp4 run measures the fp8 groups of the same weights itself)")
     settings = []
     for spec in args.sample:
         f = spec.split(",")
@@ -123,6 +146,10 @@ def main():
         args.out = os.path.join(root, "profiles", f"stream_group_sampling_{args.model}.json")
     if args.llm_fp8 and not args.kernels_only and not args.fold and args.out is None:
         stem = "stream_group_prefill_fp8" if args.prefill_fp8 else "stream_group_fp8"
+        args.out = os.path.join(root, "profiles", f"{stem}_{args.model}.json")
+
+    if args.llm_fp4 and not args.kernels_only and not args.fold and args.out is None:
+        stem = "stream_group_prefill_fp4" if args.prefill_fp4 else "stream_group_fp4"
         args.out = os.path.join(root, "profiles", f"{stem}_{args.model}.json")
 
     cfg = {"2b": C.qwen2_vl_2b, "7b": C.qwen2_vl_7b, "tiny": C.tiny}[args.model]()
@@ -143,7 +170,8 @@ def main():
     n_chunks = fill + steps
     sd = random_state_dict(cfg, 0, dev)
     model = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens, llm_fp8=args.llm_fp8,
-                               **(dict(prefill_fp8=True) if args.prefill_fp8 else {}))
+                               **(dict(prefill_fp8=True) if args.prefill_fp8 else {}), **(dict(llm_fp4=True) if args.llm_fp4 else {}),
+                               **(dict(prefill_fp4=True) if args.prefill_fp4 else {}))
     eng = model._svlm_engine
     base = "Qwen2"
     torch.set_num_threads(min(torch.get_num_threads(), 8))
@@ -183,6 +211,7 @@ def main():
         torch.cuda.synchronize()
         start = [e.state.clone() - n_dec for e in engines]
         total = 0.0
+        replay_decode.rounds_ms = []   # the rounds of the last call: their spread is the noise a step is read against
         for r in range(rounds + 1):
             for e, st in zip(engines, start):
                 e.state.copy_(st)
@@ -193,6 +222,7 @@ def main():
             torch.cuda.synchronize()
             if r:                      # round 0 warms up
                 total += time.perf_counter() - t0
+                replay_decode.rounds_ms.append(1e3 * (time.perf_counter() - t0))
         return 1e3 * total / rounds
 
     proc = ResidentProcessor()
@@ -207,6 +237,9 @@ def main():
         out["solo_lookahead"] = timed(solo_run, 1, True)
         out["solo"]["decode_ms_per_chunk"] = replay_decode(eng._graph, [eng], args.new_tokens - 1)       # (its cache is still eng._last_cache)
 
+    if args.kernels_only and args.llm_fp4:
+        timed(solo_run, 1, False)      # the single-row fp4 kernels in the same trace, beside their lane-batched twins
+
     def group_passes(m, sample=None):
         groups = {}
         for B in range(1, args.max_lanes + 1):
@@ -215,6 +248,9 @@ def main():
             # the decode steps alone: the batched step graph of the last batch, one chunk's worth of replays per round
             rec["decode_ms_per_chunk"] = replay_decode(next(reversed(group._graphs.values()))[0], group.lanes, args.new_tokens - 1)
             rec["decode_us_per_step"] = 1e3 * rec["decode_ms_per_chunk"] / (args.new_tokens - 1)
+            # the rounds' median and spread beside their mean: one slow round (another process on the machine) moves the mean, not the median
+            rec["decode_us_per_step_median"] = 1e3 * statistics.median(replay_decode.rounds_ms) / (args.new_tokens - 1)
+            rec["decode_us_per_step_spread"] = 1e3 * (max(replay_decode.rounds_ms) - min(replay_decode.rounds_ms)) / (args.new_tokens - 1)
             groups[str(B)] = rec
             del group
         return groups
@@ -222,6 +258,8 @@ def main():
     groups = out["group"] = group_passes(model)
     out["llm_fp8"] = bool(args.llm_fp8)
     out["prefill_fp8"] = bool(args.prefill_fp8)
+    out["llm_fp4"] = bool(args.llm_fp4)
+    out["prefill_fp4"] = bool(args.prefill_fp4)
     out["decode_weight_bytes"] = eng.w.decode_bytes()
     if "solo" in out:
         ref = out["solo"]["frames_per_sec_median"]
@@ -250,6 +288,31 @@ def main():
             # the only margin: the solo repeats' own spread, as frames/s
             fps_solo = [p["frames_per_sec"] for p in out["solo"]["passes"]]
             out["best"].update(solo_fp8_frames_per_sec=ref, solo_fp8_frames_per_sec_spread=max(fps_solo) - min(fps_solo))
+    if args.llm_fp4:
+        # the fp8 groups (direct prefill when the fp4 model has one) and the bf16 groups of the same weights, same process, same run
+        f8 = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens, llm_fp8=True,
+                                **(dict(prefill_fp8=True) if args.prefill_fp4 else {}))
+        g8 = out["group_fp8"] = group_passes(f8)
+        out["decode_weight_bytes_fp8"] = f8._svlm_engine.w.decode_bytes()
+        del f8
+        bf = S.StreamingQwen2VL(cfg, sd, dev, max_len=max_len, max_new_tokens=args.new_tokens)
+        gb = out["group_bf16"] = group_passes(bf)
+        out["decode_weight_bytes_bf16"] = bf._svlm_engine.w.decode_bytes()
+        del bf
+        for B, rec in groups.items():
+            rec["decode_step_vs_fp8_group"] = rec["decode_us_per_step_median"] / g8[B]["decode_us_per_step_median"]
+            # the replay rounds' spread of both steps, as a fraction of the fp8 step: what the ratio is read against
+            rec["decode_step_vs_fp8_group_spread"] = (rec["decode_us_per_step_spread"] + g8[B]["decode_us_per_step_spread"]) / g8[B]["decode_us_per_step_median"]
+            rec["frames_per_sec_vs_fp8_group"] = rec["frames_per_sec"] / g8[B]["frames_per_sec"]
+            rec["decode_step_vs_bf16_group"] = rec["decode_us_per_step_median"] / gb[B]["decode_us_per_step_median"]
+            rec["frames_per_sec_vs_bf16_group"] = rec["frames_per_sec"] / gb[B]["frames_per_sec"]
+        best = lambda g: max(g, key=lambda B: g[B]["frames_per_sec"])
+        out["best"] = dict(fp4_lanes=int(best(groups)), fp4_frames_per_sec=groups[best(groups)]["frames_per_sec"],
+                           fp8_lanes=int(best(g8)), fp8_frames_per_sec=g8[best(g8)]["frames_per_sec"],
+                           bf16_lanes=int(best(gb)), bf16_frames_per_sec=gb[best(gb)]["frames_per_sec"])
+        if "solo" in out:
+            fps_solo = [p["frames_per_sec"] for p in out["solo"]["passes"]]
+            out["best"].update(solo_fp4_frames_per_sec=ref, solo_fp4_frames_per_sec_spread=max(fps_solo) - min(fps_solo))
     if settings:
         # every stream draws its tokens: the solo sampled stream and the sampling groups of the same process and run, each read against
         # its greedy counterpart above
