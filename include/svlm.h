@@ -367,6 +367,30 @@ int svlm_gemm_wfp4_norm(const void* A, int lda, const void* W4, int ldw, const v
                         int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, const void* norm_w,
                         const void* norm_b, float eps, void* XN, int ldxn, void* stream);
 
+/* ---- opt-in MX prefill (csrc/gemm_mx.hip; SvlmEngine(llm_fp4=True, prefill_mx=True)): MXFP8 activations x MXFP4 weights on the
+ * block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4).
+ * svlm_quant_mxfp8: bf16 rows x[rows, cols] (row stride ldx elements) -> OCP MXFP8: q[rows, cols] e4m3 codes (`fn` encoding, row stride
+ * ldq BYTES) and scale[rows, cols / 32] e8m0 bytes (contiguous), bit for bit weights.py:quantize_blocks_mxfp8: per block of 32 the scale
+ * 2^e with e the smallest integer such that amax <= 448 * 2^e (all-zero block e = 0, e >= -117), codes = rne_e4m3(x / 2^e), the sign
+ * kept; a block with an inf or NaN is all 0x7F with scale byte 127.  A' = e4m3(q) * 2^e is exact in bf16.  cols a multiple of 32,
+ * x and q 16-B aligned, ldx a multiple of 8, ldq of 16.
+ * replaces: nothing, the reference has bf16 activations. */
+int svlm_quant_mxfp8(const void* x, int ldx, void* q, int ldq, void* scale, int rows, int cols, void* stream);
+/* svlm_gemm_bf16 / svlm_gemm_bf16_norm on (A', W') up to the fp32 summation order: A' = e4m3(A8) * 2^(a_scale - 127) (A8 [M, K] codes,
+ * rows of lda BYTES, a_scale [M, K / 32] e8m0 bytes, contiguous: svlm_quant_mxfp8's outputs), W' = e2m1(W4) * 2^(w_scale - 127) exactly
+ * as svlm_gemm_wfp4 takes it (N rows, 2N for SVLM_ACT_SWIGLU, of ldw BYTES; w_scale [rows, K / 32] contiguous).  Both operands enter the
+ * MFMA as codes with their block scales; every product is exact and the accumulation is fp32.  Epilogue, split-K through ws and the norm
+ * inside the split-K reduce as svlm_gemm_bf16[_norm].  K a multiple of 128 (and so is the K per split), A8 and W4 16-B aligned, both
+ * scale arrays 4-B aligned, lda and ldw multiples of 16, lda >= K, ldw >= K / 2; N a multiple of 4 (8 with SVLM_ACT_SWIGLU or the norm).
+ * replaces: the prefill-row Linears (qwen2/language_forward.py:80-82,161,201) of an fp4 language model whose prefill activations are
+ * rounded to MXFP8 (a numeric mode of its own: the reference has bf16 activations). */
+int svlm_gemm_mx_a8w4(const void* A8, int lda, const void* a_scale, const void* W4, int ldw, const void* w_scale, const void* bias,
+                      const void* residual, int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes,
+                      void* stream);
+int svlm_gemm_mx_a8w4_norm(const void* A8, int lda, const void* a_scale, const void* W4, int ldw, const void* w_scale, const void* bias,
+                           const void* residual, int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes,
+                           const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn, void* stream);
+
 /* ---- stream groups: lane-batched decode step (csrc/decode_batch.hip; stream_group.py).  B = 1..4 independent streams ("lanes") on
  * one GPU and ONE weight set take their decode step together: every kernel below reads each weight row once and multiplies it with the
  * B activation rows of the group.  Per (lane, output row) the FMA order, the reductions and every bf16 rounding point are those of the

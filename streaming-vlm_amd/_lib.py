@@ -87,6 +87,9 @@ SIGNATURES = {
     "svlm_dequant_fp4_bf16": (_i, [_p, _p, _p, _i, _i, _p]),
     "svlm_gemm_wfp4": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
     "svlm_gemm_wfp4_norm": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _f, _p, _i, _p]),
+    "svlm_quant_mxfp8": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
+    "svlm_gemm_mx_a8w4": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p]),
+    "svlm_gemm_mx_a8w4_norm": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _f, _p, _i, _p]),
     "svlm_decb_embed": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
     "svlm_decb_qkv": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "svlm_decb_gate_up": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p]),

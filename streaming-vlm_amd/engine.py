@@ -38,6 +38,8 @@ FP8_PREFILL_OPS = ("gemm_wfp8", "gemm_wfp8_norm")
 FP4_LLM_OPS = ("dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4", "dequant_fp4", "gemv_fp8", "dec_lm_head_fp8")
 # ... and a prefill_fp4 engine on top of them (csrc/gemm_wfp4.hip)
 FP4_PREFILL_OPS = ("gemm_wfp4", "gemm_wfp4_norm")
+# ... or a prefill_mx engine: MXFP8 activations x the MXFP4 weights on the block-scaled MFMA (csrc/gemm_mx.hip)
+MX_PREFILL_OPS = ("quant_mxfp8", "gemm_mx_a8w4", "gemm_mx_a8w4_norm")
 
 
 @dataclass
@@ -255,7 +257,7 @@ class SvlmEngine:
                  decode_chunk: Optional[int] = None, use_graph: Optional[bool] = None, kv_slack: float = 1.0, kv_page_tokens: int = 16,
                  decode_tail: Optional[bool] = None,
                  vit_fp8: bool = False, linear_planes: Optional[bool] = None, llm_fp8: bool = False, share: Optional["SvlmEngine"] = None,
-                 prefill_fp8: bool = False, llm_fp4: bool = False, prefill_fp4: bool = False):
+                 prefill_fp8: bool = False, llm_fp4: bool = False, prefill_fp4: bool = False, prefill_mx: bool = False):
         """`share`: another engine of the same model whose WEIGHTS this one uses (language model, vision tower, embedding, lm_head,
         rope frequencies, fp8 vision images): `state_dict` is ignored and no weight tensor is copied; every per-stream buffer (sampling
         state, positions, rope table, decode scratch) is this engine's own.  A lane of a stream group is such an engine (stream_group.py).
@@ -268,11 +270,17 @@ class SvlmEngine:
         decode step streams them through the fp4 GEMVs (csrc/decode_fp4.hip), the prefill goes through the scratch layer, shared under
         the same rule.  Not with `llm_fp8`, `prefill_fp8` or `decode_tail`.
         `prefill_fp4` (with `llm_fp4`): the prefill GEMMs read the MXFP4 codes and block scales themselves (`gemm_wfp4`,
-        csrc/gemm_wfp4.hip), as `prefill_fp8` does for e4m3: no dequantisation launch, no scratch layer."""
+        csrc/gemm_wfp4.hip), as `prefill_fp8` does for e4m3: no dequantisation launch, no scratch layer.
+        `prefill_mx` (with `llm_fp4`; not with `prefill_fp4`): a numeric mode of its own.  Every prefill pass, whatever its row count,
+        rounds the A operand of its four GEMMs per layer to MXFP8 (e4m3 per block of 32 with an e8m0 scale: `quant_mxfp8`,
+        weights.py:quantize_blocks_mxfp8) and multiplies codes by codes on the block-scaled MFMA (`gemm_mx_a8w4`, csrc/gemm_mx.hip):
+        no dequantisation launch, no scratch layer.  The decode step is the `llm_fp4` one (bf16 activations, e4m3 head)."""
         if share is not None:
             if (share.cfg != cfg or torch.device(device) != share.device or bool(llm_fp8) != share.llm_fp8 or bool(vit_fp8) != share.vit_fp8
-                    or bool(prefill_fp8) != share.prefill_fp8 or bool(llm_fp4) != share.llm_fp4 or bool(prefill_fp4) != share.prefill_fp4):
-                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, llm_fp4, prefill_fp8, prefill_fp4 and vit_fp8")
+                    or bool(prefill_fp8) != share.prefill_fp8 or bool(llm_fp4) != share.llm_fp4 or bool(prefill_fp4) != share.prefill_fp4
+                    or bool(prefill_mx) != getattr(share, "prefill_mx", False)):
+                raise ValueError("share=: the engines must agree on model config, device, llm_fp8, llm_fp4, prefill_fp8, prefill_fp4, prefill_mx "
+                                 "and vit_fp8")
             ops = share.ops if ops is None else ops
         if ops is None:
             from .ops import HipOps
@@ -331,6 +339,23 @@ class SvlmEngine:
             for name, K in (("hidden", tc_.hidden_size), ("q width", tc_.num_heads * tc_.head_dim), ("intermediate", tc_.intermediate_size)):
                 if K % 64:
                     raise ValueError(f"prefill_fp4=True needs every GEMM K to be a multiple of 64 (one K-tile of the kernel): {name} is {K}")
+        # opt-in on top of llm_fp4, instead of prefill_fp4: MXFP8 activations x MXFP4 weights on v_mfma_scale_f32_16x16x128_f8f6f4.  The
+        # prefill then computes the bf16 GEMMs on (A', W') with A' = weights.dequantize_blocks_mxfp8(quantize_blocks_mxfp8(A)): the
+        # activations of every prefill GEMM are rounded to e4m3 per block of 32, in every pass, so the model does not depend on the pass size
+        self.prefill_mx = bool(prefill_mx)
+        if self.prefill_mx:
+            if not self.llm_fp4:
+                raise ValueError("prefill_mx=True needs llm_fp4=True (it multiplies MXFP8 activations with the MXFP4 language-model weights)")
+            if self.prefill_fp4:
+                raise ValueError("prefill_mx=True cannot be combined with prefill_fp4=True (two prefills of the same weights: bf16 or MXFP8 "
+                                 "activations)")
+            missing = [m for m in MX_PREFILL_OPS if not hasattr(ops, m)]
+            if missing:
+                raise ValueError(f"prefill_mx=True needs an ops backend with the MX quantiser and GEMMs; {type(ops).__name__} lacks {missing}")
+            tc_ = cfg.text
+            for name, K in (("hidden", tc_.hidden_size), ("q width", tc_.num_heads * tc_.head_dim), ("intermediate", tc_.intermediate_size)):
+                if K % 128:
+                    raise ValueError(f"prefill_mx=True needs every GEMM K to be a multiple of 128 (one K-step of the scaled MFMA): {name} is {K}")
         self._head_fp8 = self.llm_fp8 or self.llm_fp4          # the lm_head is e4m3 in both
         self.w = share.w if share is not None else EngineWeights(state_dict, cfg, self.device, llm_fp8=self.llm_fp8, llm_fp4=self.llm_fp4)
         self._fp8_scratch = None           # llm_fp8 / llm_fp4: the bf16 image of one layer the prefill GEMMs read (allocated by the first prefill)
@@ -642,7 +667,26 @@ class SvlmEngine:
         direct = self.prefill_fp8 and (self.PREFILL_FP8_MAX_ROWS is None or T <= self.PREFILL_FP8_MAX_ROWS)
         # ... or on the MXFP4 codes and block scales
         direct4 = self.prefill_fp4 and (self.PREFILL_FP4_MAX_ROWS is None or T <= self.PREFILL_FP4_MAX_ROWS)
+        if self.prefill_mx:
+            # code and scale buffers of the four A operands (xn: hidden, attn: q width, hm: intermediate), once per pass
+            mq = {K: (torch.empty((T, K), dtype=torch.uint8, device=dev), torch.empty((T, K // 32), dtype=torch.uint8, device=dev))
+                  for K in {H, qd, tc.intermediate_size}}
         for li, lw in enumerate(w.layers):
+            if self.prefill_mx:          # every pass, whatever its row count: quantise the A operand, codes x codes on the scaled MFMA
+                a8, a_s = o.quant_mxfp8(xn, *mq[H])
+                o.gemm_mx_a8w4(a8, a_s, lw["qkv_w4"], lw["qkv_w_s4"], bias=lw["qkv_b"], out=qkv)
+                o.prefill_attn(qkv[:, :qd], c.pool, li, c.slot_of_dev, self.rope_cs, attn, T, L, tc.num_heads, scale,
+                               k_new=qkv[:, qd:qd + kd], v_new=qkv[:, qd + kd:], lin=lin)
+                a8, a_s = o.quant_mxfp8(attn, *mq[qd])
+                o.gemm_mx_a8w4_norm(a8, a_s, lw["o_w4"], lw["o_w_s4"], lw["ln2"], tc.rms_eps, x, xn, residual=x)
+                a8, a_s = o.quant_mxfp8(xn, *mq[H])
+                o.gemm_mx_a8w4(a8, a_s, lw["gu_w4"], lw["gu_w_s4"], out=hm, act=ACT_SWIGLU)
+                a8, a_s = o.quant_mxfp8(hm, *mq[tc.intermediate_size])
+                if li + 1 < n_layers:
+                    o.gemm_mx_a8w4_norm(a8, a_s, lw["down_w4"], lw["down_w_s4"], w.layers[li + 1]["ln1"], tc.rms_eps, x, xn, residual=x)
+                else:
+                    o.gemm_mx_a8w4(a8, a_s, lw["down_w4"], lw["down_w_s4"], residual=x, out=x)
+                continue
             if direct4:
                 o.gemm_wfp4(xn, lw["qkv_w4"], lw["qkv_w_s4"], bias=lw["qkv_b"], out=qkv)
                 o.prefill_attn(qkv[:, :qd], c.pool, li, c.slot_of_dev, self.rope_cs, attn, T, L, tc.num_heads, scale,

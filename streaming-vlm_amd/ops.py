@@ -132,7 +132,7 @@ class HipOps:
 
     def last_gemm_plan(self):
         """What the last gemm / gemm_norm / gemm_fp8 / gemm_wfp8 call of this process launched (`fp8`: 0 bf16, 1 fp8 x fp8, 2 weight-fp8,
-        3 weight-fp4: gemm_wfp4); diagnostic library only."""
+        3 weight-fp4: gemm_wfp4, 4 MX: gemm_mx_a8w4); diagnostic library only."""
         fn = getattr(self.lib, "svlm_diag_last_gemm_plan", None)
         if fn is None:
             raise _lib.SvlmError("last_gemm_plan: the product library keeps no plan note; bind HipOps to the diagnostic library")
@@ -1120,4 +1120,78 @@ class HipOps:
         self._check(self.lib.svlm_gemm_wfp4_norm(_ptr(A), A.stride(0), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias), _ptr(residual), ldr,
                                            _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _ptr(norm_w), _ptr(norm_b),
                                            float(eps), _ptr(out_norm), out_norm.stride(0), _stream()), "svlm_gemm_wfp4_norm")
+        return out, out_norm
+
+    # ------------------------------------------------------------------ MX prefill: MXFP8 activations x MXFP4 weights (csrc/gemm_mx.hip)
+    def quant_mxfp8(self, x, q=None, scale=None):
+        """bf16 (rows, cols) -> (e4m3 codes uint8 (rows, cols), e8m0 scales uint8 (rows, cols / 32)): weights.py:quantize_blocks_mxfp8."""
+        _req(x, BF16, "quant_mxfp8.x", 2)
+        rows, cols = x.shape
+        if cols % 32:
+            raise _lib.SvlmError(f"quant_mxfp8: x is {tuple(x.shape)}; the columns must be a multiple of 32 (one block)")
+        if q is None:
+            q = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
+        if scale is None:
+            scale = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+        _req(q, torch.uint8, "quant_mxfp8.q", 2); _req(scale, torch.uint8, "quant_mxfp8.scale", 2)
+        if tuple(q.shape) != (rows, cols) or tuple(scale.shape) != (rows, cols // 32) or not scale.is_contiguous():
+            raise _lib.SvlmError(f"quant_mxfp8: q {tuple(q.shape)} / scale {tuple(scale.shape)} for x {tuple(x.shape)} (scale contiguous)")
+        self._check(self.lib.svlm_quant_mxfp8(_ptr(x), x.stride(0), _ptr(q), q.stride(0), _ptr(scale), rows, cols, _stream()), "svlm_quant_mxfp8")
+        return q, scale
+
+    @staticmethod
+    def _req_mxfp8(A8, a_scale, K, name):
+        _req(A8, torch.uint8, f"{name}.A8", 2); _req(a_scale, torch.uint8, f"{name}.a_scale", 2)
+        M = A8.shape[0]
+        if A8.shape[1] != K or K % 128 or A8.stride(0) % 16 or tuple(a_scale.shape) != (M, K // 32) or not a_scale.is_contiguous():
+            raise _lib.SvlmError(f"{name}: A8 is {tuple(A8.shape)} (stride {A8.stride(0)}) with scales {tuple(a_scale.shape)} but W4 holds K = {K} "
+                                 "codes per row; K must be a multiple of 128, the row stride of 16, the scales [M, K / 32] contiguous")
+        return M
+
+    def gemm_mx_a8w4(self, A8, a_scale, W4, w_scale, bias=None, residual=None, out=None, act=ACT_NONE):
+        """`gemm` on (A', W') = (e4m3 codes * 2^e, e2m1 codes * 2^e) on the block-scaled MFMA; K % 128 == 0."""
+        N, K = self._req_fp4(W4, w_scale, "gemm_mx_a8w4")
+        M = self._req_mxfp8(A8, a_scale, K, "gemm_mx_a8w4")
+        if act == ACT_SWIGLU:          # W4 = [gate rows; up rows]: the output has half as many columns
+            if N % 2 or residual is not None or (bias is not None and bias.numel() != N):
+                raise _lib.SvlmError("gemm_mx_a8w4: ACT_SWIGLU takes W4 = [gate; up] (even row count), bias = [gate; up], no residual")
+            N //= 2
+        if out is None:
+            out = torch.empty((M, N), dtype=BF16, device=A8.device)
+        _req(out, BF16, "gemm_mx_a8w4.out", 2)
+        if tuple(out.shape) != (M, N):
+            raise _lib.SvlmError(f"gemm_mx_a8w4: out shape {tuple(out.shape)} != {(M, N)}")
+        if bias is not None:
+            _req(bias, BF16, "gemm_mx_a8w4.bias", 1)
+            assert bias.numel() == (2 * N if act == ACT_SWIGLU else N)
+        ldr = 0
+        if residual is not None:
+            _req(residual, BF16, "gemm_mx_a8w4.residual", 2)
+            assert tuple(residual.shape) == (M, N)
+            ldr = residual.stride(0)
+        ws = self._ws(A8.device)
+        self._check(self.lib.svlm_gemm_mx_a8w4(_ptr(A8), A8.stride(0), _ptr(a_scale), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias),
+                                         _ptr(residual), ldr, _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4, _stream()),
+                    "svlm_gemm_mx_a8w4")
+        return out
+
+    def gemm_mx_a8w4_norm(self, A8, a_scale, W4, w_scale, norm_w, eps, out, out_norm, bias=None, residual=None, act=ACT_NONE, norm_b=None):
+        """`gemm_norm` on (A', W') on the block-scaled MFMA."""
+        _req(out, BF16, "gemm_mx_a8w4_norm.out", 2)
+        _req(out_norm, BF16, "gemm_mx_a8w4_norm.out_norm", 2); _req(norm_w, BF16, "gemm_mx_a8w4_norm.norm_w", 1)
+        N, K = self._req_fp4(W4, w_scale, "gemm_mx_a8w4_norm")
+        M = self._req_mxfp8(A8, a_scale, K, "gemm_mx_a8w4_norm")
+        assert tuple(out.shape) == (M, N) == tuple(out_norm.shape) and norm_w.numel() == N
+        ldr = 0
+        if residual is not None:
+            _req(residual, BF16, "gemm_mx_a8w4_norm.residual", 2)
+            assert tuple(residual.shape) == (M, N)
+            ldr = residual.stride(0)
+        if bias is not None:
+            _req(bias, BF16, "gemm_mx_a8w4_norm.bias", 1)
+        ws = self._ws(A8.device)
+        self._check(self.lib.svlm_gemm_mx_a8w4_norm(_ptr(A8), A8.stride(0), _ptr(a_scale), _ptr(W4), W4.stride(0), _ptr(w_scale), _ptr(bias),
+                                              _ptr(residual), ldr, _ptr(out), out.stride(0), M, N, K, act, _ptr(ws), ws.numel() * 4,
+                                              _ptr(norm_w), _ptr(norm_b), float(eps), _ptr(out_norm), out_norm.stride(0), _stream()),
+                    "svlm_gemm_mx_a8w4_norm")
         return out, out_norm

@@ -195,7 +195,8 @@ class StreamGroup:
             SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
                        use_graph=engine.use_graph, kv_slack=engine.kv_slack, kv_page_tokens=engine.kv_page_tokens, decode_tail=False,
                        vit_fp8=engine.vit_fp8, linear_planes=engine.linear_planes, llm_fp8=engine.llm_fp8, share=engine,
-                       prefill_fp8=engine.prefill_fp8, llm_fp4=engine.llm_fp4, prefill_fp4=engine.prefill_fp4)
+                       prefill_fp8=engine.prefill_fp8, llm_fp4=engine.llm_fp4, prefill_fp4=engine.prefill_fp4,
+                       prefill_mx=getattr(engine, "prefill_mx", False))
             for _ in range(self.n_lanes - 1)]
         for ln in self.lanes[1:]:
             ln.default_top_k, ln.default_top_p, ln.eos_dev = engine.default_top_k, engine.default_top_p, engine.eos_dev

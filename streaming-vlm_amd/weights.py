@@ -211,6 +211,42 @@ def dequantize_blocks_mxfp4(codes: torch.Tensor, scales: torch.Tensor, dtype=tor
     return torch.ldexp(vals, (scales.to(torch.int32) - 127).unsqueeze(2)).view(N, K).to(dtype)
 
 
+def quantize_blocks_mxfp8(x: torch.Tensor):
+    """OCP MXFP8 (e4m3 elements) of a bf16 [M, K] activation matrix, K a multiple of 32: per block of 32 consecutive K elements one scale
+    2^e with e the smallest integer such that amax(block) <= 448 * 2^e (from the exponent and mantissa of amax, no division: with
+    amax = m * 2^ex, m in [0.5, 1), e = ex - 9 if m <= 0.875 else ex - 8; nothing ever saturates), an all-zero block e = 0, e clamped
+    below at -117 (quieter blocks round toward zero and every non-zero A' stays a normal bf16; bf16 inputs cannot overflow e8m0 above);
+    codes = round-to-nearest-even of x / 2^e (exact: a power of two on an 8-bit significand) onto e4m3 in the `fn` encoding
+    (torch.float8_e4m3fn), the sign kept (a -0 or a negative value that rounds to zero is 0x80).  A block that holds an inf or a NaN is
+    code 0x7F (NaN) in every element with scale byte 127.  Returns (codes uint8 [M, K], scales uint8 [M, K / 32]), scale byte = e + 127.
+    A' = e4m3(code) * 2^e is exactly representable in bf16."""
+    if x.dim() != 2 or x.shape[1] % 32:
+        raise ValueError(f"quantize_blocks_mxfp8: needs a [M, K] matrix with K a multiple of 32 (one block = 32 elements), got {tuple(x.shape)}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_blocks_mxfp8: needs bf16 activations, got {x.dtype}")
+    M, K = x.shape
+    xf = x.detach().float().view(M, K // 32, 32)
+    amax = xf.abs().amax(dim=2)                              # (a NaN propagates)
+    bad = ~torch.isfinite(amax)
+    amax = torch.where(bad, torch.zeros_like(amax), amax)
+    xf = torch.where(bad.unsqueeze(2), torch.zeros_like(xf), xf)
+    m, ex = torch.frexp(amax)                                # amax = m * 2^ex, m in [0.5, 1); 448 * 2^e = 0.875 * 2^(e + 9)
+    e = torch.where(m <= 0.875, ex - 9, ex - 8)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(min=-117)
+    a = torch.ldexp(xf.double(), -e.unsqueeze(2)).float()    # x / 2^e, |.| <= 448, exact (fp64 keeps 2^-e and the product normal)
+    codes = a.to(torch.float8_e4m3fn).view(torch.uint8)
+    codes = torch.where(bad.unsqueeze(2), torch.full_like(codes, 0x7F), codes).view(M, K).contiguous()
+    scales = torch.where(bad, torch.full_like(e, 127), e + 127).to(torch.uint8).contiguous()
+    return codes, scales
+
+
+def dequantize_blocks_mxfp8(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16):
+    """A' = e4m3(code) * 2^(scale - 127), [M, K] from codes [M, K] and scales [M, K / 32] (exact in bf16; a NaN code stays NaN)."""
+    M, K = codes.shape
+    vals = codes.contiguous().view(torch.float8_e4m3fn).float().view(M, K // 32, 32)
+    return torch.ldexp(vals.double(), (scales.to(torch.int32) - 127).unsqueeze(2)).view(M, K).to(dtype)
+
+
 def fp4_reference_state_dict(sd: Dict[str, torch.Tensor], cfg: ModelConfig) -> Dict[str, torch.Tensor]:
     """The model an `llm_fp4=True` engine built from `sd` computes, as a bf16 state dict: every LLM layer matrix (q/k/v/o_proj,
     gate/up/down_proj) replaced by its MXFP4 W' = dequant(quant(W)), the lm_head by its e4m3 W' exactly as `fp8_reference_state_dict`

@@ -1,6 +1,6 @@
 """The opt-in MXFP4 language model (SvlmEngine(llm_fp4=True)) against the bf16 default and the fp8 engine on the bench streams.
 
-    python tools/llm_fp4_stream.py [2b|7b ...] [--steps K] [--warmup W] [--repeats R] [--out DIR] [--no-kernels] [--prefill-fp4]
+    python tools/llm_fp4_stream.py [2b|7b ...] [--steps K] [--warmup W] [--repeats R] [--out DIR] [--no-kernels] [--prefill-fp4 | --prefill-mx]
 
 Per model ONE child process builds the bf16, the fp8 (scratch-layer prefill) and the fp4 model and runs their streams in alternation
 (tools/llm_fp8_stream.py:stream_run: the window is filled first, then K chunks are timed as bench.py does), `--repeats` times each.  The
@@ -12,7 +12,11 @@ layers of distinct weights, cold (512 MiB written between replays), bytes being 
 `--prefill-fp4`: the alternating set becomes bf16, fp8 with the direct prefill (prefill_fp8=True), fp4 with the scratch-layer prefill and
 fp4 with the direct prefill (prefill_fp4=True: the prefill GEMMs read the MXFP4 weights, csrc/gemm_wfp4.hip); no kernel child; the
 record goes to profiles/llm_fp4_prefill_<model>.json and its summary holds the direct - scratch prefill difference per chunk against
-the largest repeat spread."""
+the largest repeat spread.
+
+`--prefill-mx`: the four passes of --prefill-fp4 plus fp4 with the MX prefill (prefill_mx=True: MXFP8 activations x MXFP4 weights on the
+block-scaled MFMA, csrc/gemm_mx.hip; its four quantiser launches per layer are inside its prefill time), same run; the record goes to
+profiles/llm_fp4_prefill_mx_<model>.json and its summary holds the MX prefill's difference to each of the four."""
 import argparse
 import json
 import os
@@ -29,6 +33,7 @@ import llm_fp8_stream as F8          # noqa: E402  (stream_run, the stream geome
 FORMS = {"bf16": {}, "fp8": dict(llm_fp8=True), "fp4": dict(llm_fp4=True)}
 PREFILL_FORMS = {"bf16": {}, "fp8_direct": dict(llm_fp8=True, prefill_fp8=True), "fp4": dict(llm_fp4=True),
                  "fp4_direct": dict(llm_fp4=True, prefill_fp4=True)}
+MX_FORMS = dict(PREFILL_FORMS, fp4_mx=dict(llm_fp4=True, prefill_mx=True))
 
 
 def build(model_name, **kw):
@@ -44,14 +49,15 @@ def build(model_name, **kw):
     return S.StreamingQwen2VL(cfg, random_state_dict(cfg, 0, dev), dev, max_len=max_len, max_new_tokens=F8.NEW, **kw)
 
 
-def stream_runs(model_name, steps, warmup, repeats, prefill_fp4=False):
-    FORMS = PREFILL_FORMS if prefill_fp4 else globals()["FORMS"]
+def stream_runs(model_name, steps, warmup, repeats, prefill_fp4=False, prefill_mx=False):
+    FORMS = MX_FORMS if prefill_mx else PREFILL_FORMS if prefill_fp4 else globals()["FORMS"]
+    prefill_fp4 = prefill_fp4 or prefill_mx
     models = {name: build(model_name, **kw) for name, kw in FORMS.items()}
     passes = {k: [] for k in FORMS}
     for r in range(repeats):
         for name in FORMS:
             rec, _ = F8.stream_run(model_name, name.startswith("fp8"), steps, warmup, model=models[name])
-            rec.update(form=name, repeat=r, llm_fp4=name.startswith("fp4"), prefill_fp4=name == "fp4_direct", prefill_fp8=name == "fp8_direct",
+            rec.update(form=name, repeat=r, llm_fp4=name.startswith("fp4"), prefill_fp4=name == "fp4_direct", prefill_fp8=name == "fp8_direct", prefill_mx=name == "fp4_mx",
                        decode_us_per_step=round(1e3 * rec["decode_ms_per_chunk"] / max(rec["decode_steps_per_chunk"], 1), 2))
             del rec["build_seconds"]
             passes[name].append(rec)
@@ -70,6 +76,11 @@ def stream_runs(model_name, steps, warmup, repeats, prefill_fp4=False):
         summ["prefill_ms_direct_minus_fp8_direct"] = round(pf("fp4_direct")["median"] - pf("fp8_direct")["median"], 3)
         summ["prefill_ms_repeat_spread"] = max(pf(n)["spread"] for n in FORMS)
         summ["scratch_layer_allocated"] = {n: models[n]._svlm_engine._fp8_scratch is not None for n in FORMS}
+        if prefill_mx:
+            summ["run"] = "fp4_prefill_mx_summary"
+            for n in PREFILL_FORMS:
+                summ[f"prefill_ms_mx_minus_{n}"] = round(pf("fp4_mx")["median"] - pf(n)["median"], 3)
+            summ["quantiser_launches_per_prefill"] = 4 * len(models["fp4_mx"]._svlm_engine.w.layers)
         return lines + [summ]
     du = lambda n: summ[f"{n}.decode_us_per_step"]
     summ["decode_us_fp4_minus_fp8"] = round(du("fp4")["median"] - du("fp8")["median"], 2)
@@ -152,18 +163,19 @@ def main():
     ap.add_argument("--out", default=None, help="directory: one llm_fp4_<model>.json per model (all of its lines)")
     ap.add_argument("--no-kernels", action="store_true", help="skip the per-kernel child")
     ap.add_argument("--prefill-fp4", action="store_true", help="bf16, direct fp8, scratch fp4 and direct fp4 (prefill_fp4=True) streams")
+    ap.add_argument("--prefill-mx", action="store_true", help="the --prefill-fp4 passes plus fp4 with the MX prefill (prefill_mx=True)")
     ap.add_argument("--child", nargs=2, metavar=("MODEL", "RUN"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         m, run = args.child
-        for line in ([kernel_run(m)] if run == "kernels" else stream_runs(m, args.steps, args.warmup, args.repeats, args.prefill_fp4)):
+        for line in ([kernel_run(m)] if run == "kernels" else stream_runs(m, args.steps, args.warmup, args.repeats, args.prefill_fp4, args.prefill_mx)):
             print(json.dumps(line), flush=True)
         return
     for m in args.models:
         lines = []
-        for run in ("streams",) + (() if args.no_kernels or args.prefill_fp4 else ("kernels",)):
+        for run in ("streams",) + (() if args.no_kernels or args.prefill_fp4 or args.prefill_mx else ("kernels",)):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--repeats",
-                                str(args.repeats), *(["--prefill-fp4"] if args.prefill_fp4 else []), "--child", m, run],
+                                str(args.repeats), *(["--prefill-fp4"] if args.prefill_fp4 else []), *(["--prefill-mx"] if args.prefill_mx else []), "--child", m, run],
                                capture_output=True, text=True)
             if p.returncode != 0:
                 sys.stderr.write(p.stderr[-4000:])
@@ -174,7 +186,8 @@ def main():
             lines += new
         if args.out:
             os.makedirs(args.out, exist_ok=True)
-            with open(os.path.join(args.out, f"llm_fp4_prefill_{m}.json" if args.prefill_fp4 else f"llm_fp4_{m}.json"), "w") as f:
+            fname = f"llm_fp4_prefill_mx_{m}.json" if args.prefill_mx else f"llm_fp4_prefill_{m}.json" if args.prefill_fp4 else f"llm_fp4_{m}.json"
+            with open(os.path.join(args.out, fname), "w") as f:
                 json.dump(lines, f, indent=1)
 
 
