@@ -435,6 +435,40 @@ int svlm_decb_lm_head(const void* lanes, int B, const void* x, int ldx, const vo
                       int ldl, const int* suppress, void* ws, int V, int K, void* stream);
 int svlm_decb_argmax_finish(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream);
 
+/* ---- wide stream groups (csrc/decode_wide.hip; StreamGroup(wide=True)): the bf16 weight kernels of the batched decode step as skinny
+ * GEMMs on the matrix cores, for B = 1..16 lanes and the same lane table.  A workgroup multiplies a tile of 16 weight rows (A operand
+ * of v_mfma_f32_16x16x32_bf16) with the activation rows of up to 16 lanes (B operand, one lane per column): the cost is flat in B.
+ * The normalised rows are bit for bit those of the svlm_decb_* / svlm_dec_* entries and every bf16 rounding point is kept; only the
+ * summation order of the dot products differs (MFMA blocks of 32, K split over the waves of the workgroup and summed in a fixed order:
+ * deterministic, no atomics).  LANE INDEPENDENCE: a live lane's outputs are a function of that lane's inputs alone -- not of B, of
+ * the column it sits in or of what other lanes hold.  A lane that is not live is never written.
+ * B in 1..16; K a multiple of 8; leading dimensions as the svlm_decb_* entries; the three entries that stage the normalised rows need
+ * K <= 4096 and B * (K + 8 or 16) * 2 <= 120 KB of LDS. */
+int svlm_decw_max_lanes(void); /* [host] 16 */
+/* [host] the K split of an entry (fused != 0: qkv / gate_up / lm_head; 0: gemv): *splits partial sums per output, each over at most
+ * *kps consecutive k.  A function of K alone. */
+int svlm_decw_plan(int fused, int K, int* splits, int* kps);
+/* opts the staging kernels into more than 64 KB of dynamic LDS (done on first need; a group calls it before it captures a graph) */
+int svlm_decw_reserve_lds(void);
+/* svlm_decb_embed for 1..16 lanes (the same kernel).  replaces: the embed_tokens call of a decode step (qwen2/model_forward.py:33). */
+int svlm_decw_embed(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream);
+/* svlm_decb_qkv on the MFMA: K/V rows land exactly where svlm_decb_qkv puts them.
+ * replaces: qwen2/language_forward.py:183,80-82 + generate/streaming_cache.py:72-73. */
+int svlm_decw_qkv(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw, const void* bias,
+                  void* q_out, int ldq, int layer, int K, int qd, int kd, int D, void* stream);
+/* svlm_decb_gate_up on the MFMA.  replaces: qwen2/language_forward.py:200-201 (Qwen2MLP). */
+int svlm_decw_gate_up(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw, void* h,
+                      int ldh, int I, int K, void* stream);
+/* svlm_decb_gemv on the MFMA.  replaces: o_proj / down_proj at T = 1 (qwen2/language_forward.py:161,201). */
+int svlm_decw_gemv(const void* lanes, int B, const void* x, int ldx, const void* W, int ldw, const void* residual, int ldr, void* y,
+                   int ldy, int N, int K, void* stream);
+/* svlm_decb_lm_head on the MFMA: the candidates in the same workspace (one per 8 vocabulary rows, svlm_decb_lm_head_ws_stride(V) bytes
+ * per lane), completed by svlm_decw_argmax_finish (the finish kernel of svlm_decb_argmax_finish for 1..16 lanes).
+ * replaces: qwen2/language_forward.py:315, qwen2/model_forward.py:243, generate/streaming_generate_qwen.py:73-104. */
+int svlm_decw_lm_head(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw, float* logits,
+                      int ldl, const int* suppress, void* ws, int V, int K, void* stream);
+int svlm_decw_argmax_finish(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream);
+
 /* ---- stream groups on fp8 language-model weights (csrc/decode_batch_fp8.hip): the lane-batched twins of the single-row fp8 entries
  * above, with W8 + w_scale in place of W.  Per (lane, output row) every output is BITWISE what the single-row fp8 entry computes for
  * the lane alone; each 16-code weight vector is converted to fp32 once for all B lanes.  Same lane table, same skipping of a lane

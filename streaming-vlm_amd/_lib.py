@@ -97,6 +97,15 @@ SIGNATURES = {
     "svlm_decb_lm_head_ws_stride": (_ll, [_i]),
     "svlm_decb_lm_head": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_decb_argmax_finish": (_i, [_p, _i, _p, _i, _i, _p]),
+    "svlm_decw_max_lanes": (_i, []),
+    "svlm_decw_plan": (_i, [_i, _i, _p, _p]),
+    "svlm_decw_reserve_lds": (_i, []),
+    "svlm_decw_embed": (_i, [_p, _i, _p, _i, _p, _i, _i, _p]),
+    "svlm_decw_qkv": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "svlm_decw_gate_up": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p]),
+    "svlm_decw_gemv": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
+    "svlm_decw_lm_head": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
+    "svlm_decw_argmax_finish": (_i, [_p, _i, _p, _i, _i, _p]),
     "svlm_decb_qkv_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "svlm_decb_gate_up_fp8": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p]),
     "svlm_decb_gemv_fp8": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),

@@ -31,6 +31,12 @@ struct svlm_lane_sample {          // mirror of include/svlm.h
 static_assert(sizeof(svlm_lane_sample) == 24, "svlm_lane_sample layout (include/svlm.h)");
 enum { SVLM_SAMPLE_GREEDY = 0, SVLM_SAMPLE_GUMBEL = 1, SVLM_SAMPLE_FILTERED = 2, SVLM_SAMPLE_NUCLEUS = 3 };
 
+// host side, defined in decode_batch.hip: the candidate workspace stride, and the launches of the embed and finish kernels without the
+// B <= 4 check of their entries (shared with the wide entries of decode_wide.hip)
+extern "C" long long svlm_decb_lm_head_ws_stride(int V);
+void decb_embed_launch(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream);
+void decb_argmax_finish_launch(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream);
+
 __device__ __forceinline__ bool lane_live(const svlm_lane& L) { return L.state[1] + 1 < L.limit; }
 
 // Prologue of the fused kernels: the live lanes' x rows are requested first, then the head of the weight stream, then the rows are

@@ -477,11 +477,22 @@ static inline bool decb_ok(int B, int K, int ldx) { return B >= 1 && B <= 4 && K
     else KERNEL<4, ROWS> __VA_ARGS__;                                       \
   } while (0)
 
+// The two launches whose geometry is one grid row / one workgroup PER LANE and nothing else of B: the entries below keep B <= 4, the
+// wide entries (decode_wide.hip) check 1..16 and launch the same kernels through these (declared in dec_lanes.h).
+void decb_embed_launch(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream) {
+  decb_embed_kernel<<<dim3((cols / 8 + 255) / 256, B), 256, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const bf16_t*)table,
+                                                                                      (bf16_t*)x, ldx, cols, n_rows);
+}
+void decb_argmax_finish_launch(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream) {
+  const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
+  decb_argmax_finish_kernel<<<B, 1024, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const float*)ws, svlm_decb_lm_head_ws_stride(V), nb,
+                                                                 advance_kv);
+}
+
 extern "C" int svlm_decb_embed(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && B >= 1 && B <= 4 && n_rows > 0 && cols > 0 && cols % 8 == 0 && ldx >= cols && ldx % 8 == 0,
                  "svlm_decb_embed: bad B=%d n_rows=%d cols=%d ldx=%d", B, n_rows, cols, ldx);
-  decb_embed_kernel<<<dim3((cols / 8 + 255) / 256, B), 256, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const bf16_t*)table,
-                                                                                      (bf16_t*)x, ldx, cols, n_rows);
+  decb_embed_launch(lanes, B, table, n_rows, x, ldx, cols, stream);
   return svlm_check_launch("svlm_decb_embed");
 }
 
@@ -547,9 +558,7 @@ extern "C" int svlm_decb_lm_head(const void* lanes, int B, const void* x, int ld
 
 extern "C" int svlm_decb_argmax_finish(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && B >= 1 && B <= 4 && V > 0 && ws != nullptr, "svlm_decb_argmax_finish: bad args");
-  const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
-  decb_argmax_finish_kernel<<<B, 1024, 0, (hipStream_t)stream>>>((const svlm_lane*)lanes, (const float*)ws, svlm_decb_lm_head_ws_stride(V), nb,
-                                                                 advance_kv);
+  decb_argmax_finish_launch(lanes, B, ws, V, advance_kv, stream);
   return svlm_check_launch("svlm_decb_argmax_finish");
 }
 

@@ -74,7 +74,7 @@ class StreamGroupError(RuntimeError):
 
 
 def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Optional[int] = None, group=None, sampling: bool = False,
-                              **common_kw) -> List:
+                              wide: bool = False, **common_kw) -> List:
     """Run `len(streams)` streams on ONE GPU through a stream group: each entry of `streams` holds the per-stream keyword arguments of
     `streaming_inference` (video_path, query, previous_text, duration, ...), `common_kw` the shared ones.  Every stream runs the
     unchanged `streaming_inference` loop in its own host thread against its lane's model object; the lanes' generate() calls meet in
@@ -84,14 +84,16 @@ def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Op
     Token choice: greedy only by default (pass do_sample=False, or top_k=1); with `sampling=True` the group is built as
     `StreamGroup(..., sampling=True)` and every stream may carry its own `do_sample / temperature / top_k / top_p / generator` -- each
     lane then produces the tokens of that stream run alone on a fresh model with the same generator seed (an existing `group` passed in
-    keeps the setting it was built with).  Strict-causal (no look-ahead ViT).  Returns the per-stream response
+    keeps the setting it was built with).  `wide=True` builds `StreamGroup(..., wide=True)`: up to 16 lanes on the MFMA decode kernels
+    (bf16 weights, greedy; `n_lanes` still defaults to min(3, streams)).  Strict-causal (no look-ahead ViT).  Returns the per-stream response
     lists in the order of `streams`; if a stream raised, the others still run to their end and a `StreamGroupError` naming the first
     failed stream's index is raised afterwards."""
     import threading
     from .driver import streaming_inference
     from .stream_group import DEFAULT_LANES, StreamGroup
     if group is None:
-        group = StreamGroup(model._svlm_engine, min(DEFAULT_LANES, len(streams)) if n_lanes is None else n_lanes, sampling=sampling)
+        group = StreamGroup(model._svlm_engine, min(DEFAULT_LANES, len(streams)) if n_lanes is None else n_lanes, sampling=sampling,
+                            wide=wide)
     results: List = [None] * len(streams)
     errors = {}
     lock = threading.Lock()

@@ -799,6 +799,70 @@ class HipOps:
         self._check(self.lib.svlm_decb_sample_finish(_ptr(lanes), _ptr(samples), B, _ptr(logits), ldl, _ptr(suppress), _ptr(ws), int(V),
                                                int(advance_kv), _stream()), "svlm_decb_sample_finish")
 
+    # ------------------------------------------------------------------ wide lane-batched decode step (csrc/decode_wide.hip)
+    # The decb_* weight kernels as skinny GEMMs on the MFMA, for 1..16 lanes: same lane table, same operands, same workspace.
+    def decw_max_lanes(self):
+        return int(self.lib.svlm_decw_max_lanes())
+
+    def decw_plan(self, fused, K):
+        """(splits, kps): how an entry splits K (fused: qkv / gate_up / lm_head; otherwise gemv) -- a function of K alone."""
+        import ctypes
+        sp, kps = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self.lib.svlm_decw_plan(int(bool(fused)), int(K), ctypes.addressof(sp), ctypes.addressof(kps)), "svlm_decw_plan")
+        return sp.value, kps.value
+
+    def decw_reserve_lds(self):
+        self._check(self.lib.svlm_decw_reserve_lds(), "svlm_decw_reserve_lds")
+
+    def _lanes_w(self, lanes, B, what):
+        _req(lanes, torch.int64, what + ".lanes", 2)
+        if not (1 <= B <= 16 and lanes.shape[0] >= B and lanes.shape[1] == self.LANE_WORDS and lanes.is_contiguous()):
+            raise _lib.SvlmError(f"{what}: lane table {tuple(lanes.shape)} for B={B} (1..16 lanes of {self.LANE_WORDS} words)")
+
+    def decw_embed(self, lanes, B, table, x):
+        self._lanes_w(lanes, B, "decw_embed"); _req(table, BF16, "decw_embed.table", 2)
+        assert table.is_contiguous()
+        ldx = self._rows(x, B, table.shape[1], "decw_embed.x")
+        self._check(self.lib.svlm_decw_embed(_ptr(lanes), B, _ptr(table), table.shape[0], _ptr(x), ldx, table.shape[1], _stream()), "svlm_decw_embed")
+
+    def decw_qkv(self, lanes, B, x, ln_w, eps, W, bias, q_out, layer, qd, kd, D, n_layers):
+        self._lanes_w(lanes, B, "decw_qkv"); _req(ln_w, BF16, "decw_qkv.ln_w", 1); _req(W, BF16, "decw_qkv.W", 2); _req(bias, BF16, "decw_qkv.bias", 1)
+        N, K = W.shape
+        assert N == qd + 2 * kd == bias.numel() and ln_w.numel() == K and 0 <= layer < n_layers
+        ldx, ldq = self._rows(x, B, K, "decw_qkv.x"), self._rows(q_out, B, qd, "decw_qkv.q_out")
+        self._check(self.lib.svlm_decw_qkv(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(bias), _ptr(q_out), ldq,
+                                     int(layer), K, qd, kd, D, _stream()), "svlm_decw_qkv")
+
+    def decw_gate_up(self, lanes, B, x, ln_w, eps, W, h):
+        self._lanes_w(lanes, B, "decw_gate_up"); _req(ln_w, BF16, "decw_gate_up.ln_w", 1); _req(W, BF16, "decw_gate_up.W", 2)
+        N, K = W.shape
+        assert N % 2 == 0 and ln_w.numel() == K
+        ldx, ldh = self._rows(x, B, K, "decw_gate_up.x"), self._rows(h, B, N // 2, "decw_gate_up.h")
+        self._check(self.lib.svlm_decw_gate_up(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(h), ldh, N // 2, K,
+                                         _stream()), "svlm_decw_gate_up")
+
+    def decw_gemv(self, lanes, B, x, W, residual, out):
+        self._lanes_w(lanes, B, "decw_gemv"); _req(W, BF16, "decw_gemv.W", 2)
+        N, K = W.shape
+        ldx, ldr, ldy = self._rows(x, B, K, "decw_gemv.x"), self._rows(residual, B, N, "decw_gemv.residual"), self._rows(out, B, N, "decw_gemv.out")
+        self._check(self.lib.svlm_decw_gemv(_ptr(lanes), B, _ptr(x), ldx, _ptr(W), W.stride(0), _ptr(residual), ldr, _ptr(out), ldy, N, K, _stream()),
+              "svlm_decw_gemv")
+
+    def decw_lm_head(self, lanes, B, x, ln_w, eps, W, logits, suppress, ws):
+        self._lanes_w(lanes, B, "decw_lm_head"); _req(ln_w, BF16, "decw_lm_head.ln_w", 1); _req(W, BF16, "decw_lm_head.W", 2)
+        _req(suppress, torch.int32, "decw_lm_head.suppress", 1); _req(ws, torch.float32, "decw_lm_head.ws", 2)
+        V, K = W.shape
+        assert ln_w.numel() == K and suppress.numel() >= 8 and ws.is_contiguous()
+        assert ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        ldx, ldl = self._rows(x, B, K, "decw_lm_head.x"), self._rows(logits, B, V, "decw_lm_head.logits", torch.float32)
+        self._check(self.lib.svlm_decw_lm_head(_ptr(lanes), B, _ptr(x), ldx, _ptr(ln_w), float(eps), _ptr(W), W.stride(0), _ptr(logits), ldl,
+                                         _ptr(suppress), _ptr(ws), V, K, _stream()), "svlm_decw_lm_head")
+
+    def decw_argmax_finish(self, lanes, B, ws, V, advance_kv):
+        self._lanes_w(lanes, B, "decw_argmax_finish"); _req(ws, torch.float32, "decw_argmax_finish.ws", 2)
+        assert ws.is_contiguous() and ws.shape[0] >= B and ws.shape[1] * 4 == self.lib.svlm_decb_lm_head_ws_stride(V)
+        self._check(self.lib.svlm_decw_argmax_finish(_ptr(lanes), B, _ptr(ws), V, int(advance_kv), _stream()), "svlm_decw_argmax_finish")
+
     # the same on e4m3 weights with per-row scales (csrc/decode_batch_fp8.hip): (W8, w_scale) where W stands; decb_embed,
     # decb_sampling_ws and decb_argmax_finish serve both
     def decb_qkv_fp8(self, lanes, B, x, ln_w, eps, W8, w_scale, bias, q_out, layer, qd, kd, D, n_layers):

@@ -1,4 +1,4 @@
-"""Stream groups: B independent streams (B = 1..4, "lanes") on one GPU and ONE weight set, whose decode steps run in lock-step through
+"""Stream groups: B independent streams (B = 1..4, "lanes"; 1..16 in a wide group, below) on one GPU and ONE weight set, whose decode steps run in lock-step through
 the lane-batched kernels of csrc/decode_batch.hip -- each weight byte is read once and each launch boundary paid once for B tokens.
 An `llm_fp8=True` engine takes the same steps through the e4m3 twins of csrc/decode_batch_fp8.hip: half the weight bytes, read once
 for B tokens, and each weight converted to fp32 once for all B lanes.  Its prefill stays per stream and dequantises layer by layer
@@ -27,6 +27,16 @@ Opt-in; nothing here is reached by the single-stream path.  Refused with a Value
 fp8 sampling head), an `llm_fp4=True` engine whose ops backend lacks the batched fp4 entry points or the batched fp8 head (with
 `sampling=True` also the fp8 sampling head), `do_sample=True` with anything but `top_k == 1` unless the group was built with `sampling=True`, `force_tokens`,
 `keep_logits`.
+
+Wide groups.  `StreamGroup(..., wide=True)` takes the same steps through the `decw_*` entries of csrc/decode_wide.hip: the weight kernels
+as skinny GEMMs on the matrix cores, whose cost is flat in the lane count, for 1..`MAX_LANES_WIDE` (16) lanes.  bf16 language-model
+weights and greedy decoding only: an `llm_fp8=True` or `llm_fp4=True` engine, `sampling=True` and an ops backend without the `decw_*`
+entry points are refused with a ValueError that names `wide=True`.  The launch sequence is the one above with `decw_` for `decb_`.  The
+wide kernels keep the normalised rows and every rounding point of the single-row kernels but sum the dot products in another order, so a
+lane is no longer bitwise the stream run alone; what holds instead is LANE INDEPENDENCE -- a lane's outputs do not depend on how many
+lanes the batch has, on the lane's place in it or on what the other lanes hold -- so a stream in a wide group of 16 is exactly the
+stream in a wide group of one.
+
 The look-ahead ViT (`next_vision`) is DECLINED: a group runs strict-causal, every chunk's vision tower runs inside its own
 `generate_begin`.
 """
@@ -49,6 +59,9 @@ MAX_LANES = 4
 # aggregate frames/s stops growing at 3 lanes on Qwen2-VL-2B (profiles/stream_group_2b.json: 4 lanes are 0.6 % below 3), so nothing picks
 # more than 3 by itself; 4 remain available on request
 DEFAULT_LANES = 3
+# a wide group (wide=True): one lane per column of the 16-wide MFMA tile (csrc/decode_wide.hip, svlm_decw_max_lanes)
+MAX_LANES_WIDE = 16
+WIDE_GROUP_OPS = ("decw_embed", "decw_qkv", "decw_gemv", "decw_gate_up", "decw_lm_head", "decw_argmax_finish")
 # ops entry points a group on an llm_fp8 engine needs (csrc/decode_batch_fp8.hip)
 FP8_GROUP_OPS = ("decb_qkv_fp8", "decb_gate_up_fp8", "decb_gemv_fp8", "decb_lm_head_fp8")
 # ... and on an llm_fp4 engine (csrc/decode_batch_fp4.hip; the lm_head of an fp4 engine is e4m3)
@@ -166,9 +179,21 @@ class LaneModel:
 
 
 class StreamGroup:
-    def __init__(self, engine: SvlmEngine, n_lanes: int = 2, sampling: bool = False):
-        if not 1 <= int(n_lanes) <= MAX_LANES:
-            raise ValueError(f"n_lanes={n_lanes} outside [1, {MAX_LANES}]")
+    def __init__(self, engine: SvlmEngine, n_lanes: int = 2, sampling: bool = False, wide: bool = False):
+        max_lanes = MAX_LANES_WIDE if wide else MAX_LANES
+        if not 1 <= int(n_lanes) <= max_lanes:
+            raise ValueError(f"n_lanes={n_lanes} outside [1, {max_lanes}]" + (" (wide=True)" if wide else ""))
+        if wide:
+            if getattr(engine, "llm_fp8", False):
+                raise ValueError("stream group: wide=True needs bf16 language-model weights; an llm_fp8=True engine is not supported")
+            if getattr(engine, "llm_fp4", False):
+                raise ValueError("stream group: wide=True needs bf16 language-model weights; an llm_fp4=True engine is not supported")
+            if sampling:
+                raise ValueError("stream group: wide=True is greedy only; sampling=True is not supported (there is no wide sampling head)")
+            missing = [m for m in WIDE_GROUP_OPS if not hasattr(getattr(engine, "ops", None), m)]
+            if missing:
+                raise ValueError(f"stream group: wide=True needs an ops backend with the wide entry points; "
+                                 f"{type(getattr(engine, 'ops', None)).__name__} lacks {missing}")
         if getattr(engine, "llm_fp8", False):
             missing = [m for m in FP8_GROUP_OPS if not hasattr(getattr(engine, "ops", None), m)]
             if missing:
@@ -190,6 +215,7 @@ class StreamGroup:
         self.engine = engine
         self.n_lanes = int(n_lanes)
         self.sampling = bool(sampling)
+        self.wide = bool(wide)
         tc, dev, o = engine.cfg.text, engine.device, engine.ops
         self.lanes: List[SvlmEngine] = [engine] + [
             SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
@@ -227,6 +253,8 @@ class StreamGroup:
             self._samples_host = torch.zeros((B, o.SAMPLE_WORDS), dtype=torch.int64)
             if dev.type == "cuda":
                 self._samples_host = self._samples_host.pin_memory()
+        if self.wide and dev.type == "cuda" and hasattr(o, "decw_reserve_lds"):
+            o.decw_reserve_lds()                 # (before any step is captured into a graph)
         self._graphs = {}
         self.max_graphs = engine.max_graphs
         self._rv = LaneRendezvous(self.n_lanes, lambda reqs: self.generate(reqs, return_exceptions=True))
@@ -284,6 +312,9 @@ class StreamGroup:
         B, qd, kd, nl = len(act), e.qd, e.kd, len(self.engine.w.layers)
         scale = 1.0 / math.sqrt(tc.head_dim)
         tab = self.table
+        if getattr(self, "wide", False):
+            self._step_wide(act, tab, B, scale)
+            return
         o.decb_embed(tab, B, w.embed, self.x)
         if e.llm_fp8:
             self._layers_fp8(act, tab, B, scale)
@@ -302,6 +333,22 @@ class StreamGroup:
             o.decb_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
             o.decb_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
         self._head(tab, B, sampled)
+
+    def _step_wide(self, act, tab, B, scale):
+        """`_step_launch` of a wide group: the same launches with the weight kernels on the MFMA (csrc/decode_wide.hip); greedy head."""
+        e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
+        qd, kd, nl = e.qd, e.kd, len(w.layers)
+        o.decw_embed(tab, B, w.embed, self.x)
+        for li, lw in enumerate(w.layers):
+            o.decw_qkv(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
+            for j, (lane, c) in enumerate(act):
+                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
+                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            o.decw_gemv(tab, B, self.attn, lw["o_w"], self.x, self.x)
+            o.decw_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
+            o.decw_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
+        o.decw_lm_head(tab, B, self.x, w.final_norm, tc.rms_eps, w.lm_head, self.logits, self.suppress, self.ws)
+        o.decw_argmax_finish(tab, B, self.ws, tc.vocab_size, 1)
 
     def _layers_fp8(self, act, tab, B, scale):
         """The layers of `_step_launch` on e4m3 weights: the same launches with the weight-streaming kernels replaced by their fp8 twins

@@ -31,6 +31,14 @@ against with prefill_fp8=True: direct fp4, direct fp8 and bf16 groups of ONE run
 group's step, and the solo sampled step against the solo greedy step (the per-token surcharge of the token choice, once per step in a
 group).  Writes profiles/stream_group_sampling_<model>.json.
 
+`--wide [--wide-lanes 1,2,4,8,12,16]`: after the passes above, the same passes through `StreamGroup(wide=True)` (csrc/decode_wide.hip: the
+weight kernels on the MFMA) at every lane count of the list ("group_wide"); per lane count the wide decode step is read against the
+existing group's step of the SAME run where that group exists (1..4 lanes), with the replay rounds' spread of both beside it.  Writes
+profiles/stream_group_wide_<model>.json.  The decw_* kernel averages PER LANE COUNT come from a trace run of its own:
+`rocprofv3 --kernel-trace -- python tools/stream_group_bench.py --wide --kernels-only`, whose kernel_trace CSV goes to --kernel-trace
+(with --fold): the kernel names do not carry the lane count, so every step's kernels are filed under the lane count its embedding
+gather's grid shows.
+
 Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- python tools/stream_group_bench.py --kernels-only`
 (a run of its own, no counters) and pass the stats CSV with --kernel-stats to have the decb_* / single-row averages folded in.
 
@@ -41,6 +49,7 @@ Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- pyth
     python tools/stream_group_bench.py --llm-fp4                                      (writes profiles/stream_group_fp4_2b.json)
     python tools/stream_group_bench.py --prefill-fp4 [--model 7b --fps 2 --window 4096]  (writes profiles/stream_group_prefill_fp4_<model>.json)
     python tools/stream_group_bench.py --sample 0.9 --sample 0.9,50,1.0               (writes profiles/stream_group_sampling_2b.json)
+    python tools/stream_group_bench.py --wide                                         (writes profiles/stream_group_wide_2b.json)
 """
 import argparse
 import csv
@@ -66,7 +75,7 @@ def weight_bytes(kernel, tc):
     e2m1 codes + e8m0 block scales for the fp4 twins, bf16 otherwise.  The residual GEMV that splits K over the waves (down_proj) is told from the plain one (o_proj) by its name / KW."""
     import re
     single4 = "decb_" not in kernel and any(k in kernel for k in ("dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4"))     # the single-row fp4 twins
-    if ("decb_" not in kernel and not single4) or "embed" in kernel or "argmax" in kernel:
+    if ("decb_" not in kernel and "decw_" not in kernel and not single4) or "embed" in kernel or "argmax" in kernel:
         return 0
     H, I, qd, kd = tc.hidden_size, tc.intermediate_size, tc.num_heads * tc.head_dim, tc.num_kv_heads * tc.head_dim
     fp8, fp4 = "_fp8" in kernel, "_fp4" in kernel
@@ -80,6 +89,8 @@ def weight_bytes(kernel, tc):
         # KW is the third template argument of the lane-batched GEMVs (NB, ROWS, KW, PRE), the second of gemv_fp4_kernel (ROWS, KW, PRE)
         m = re.search(r"<\s*\d+\s*,\s*(\d+)\s*,\s*\d+\s*>", kernel) if single4 else re.search(r"<\s*\d+\s*,\s*\d+\s*,\s*(\d+)\s*,", kernel)
         split = "ksplit" in kernel or ((fp8 or fp4) and m is not None and m.group(1) == "4")
+        if "decw_gemv" in kernel:                       # decw_gemv_kernel<KW>: the long K of down_proj takes the 16 waves
+            split = "<16>" in kernel
         n, k = (H, I) if split else (H, qd)
     else:
         return 0
@@ -93,7 +104,7 @@ def kernel_stats(path, cfg):
     rows = {}
     for r in csv.DictReader(open(path)):
         name = r.get("Name") or r.get("KernelName") or ""
-        if any(k in name for k in ("decb_", "dec_qkv_kernel", "dec_gate_up_kernel", "dec_lm_head_kernel", "gemv_bf16", "argmax_finish", "decode_attn",
+        if any(k in name for k in ("decb_", "decw_", "dec_qkv_kernel", "dec_gate_up_kernel", "dec_lm_head_kernel", "gemv_bf16", "argmax_finish", "decode_attn",
                                    "dec_qkv_fp8", "dec_gate_up_fp8", "dec_lm_head_fp8", "gemv_fp8", "dequant_fp8",
                                    "dec_qkv_fp4", "dec_gate_up_fp4", "gemv_fp4", "dequant_fp4")):
             rec = rows[name[:120]] = dict(calls=int(r["Calls"]), avg_us=float(r["AverageNs"]) / 1e3)
@@ -103,6 +114,37 @@ def kernel_stats(path, cfg):
                 rec["weight_tb_per_s"] = nbytes / (rec["avg_us"] * 1e-6) / 1e12
                 rec["weight_gb_per_s"] = 1e3 * rec["weight_tb_per_s"]
     return rows
+
+
+def kernel_trace_by_lanes(path, cfg):
+    """The lane-batched kernels (decb_* / decw_*) of a rocprofv3 kernel_trace CSV, averaged PER LANE COUNT: a step opens with the
+    embedding gather, whose grid has one row per lane, and every lane-batched kernel up to the next gather belongs to that step.
+    -> {kernel name: {lanes: {calls, avg_us[, weight_gb_per_s]}}}; the wide and the existing group's steps are told apart by their names."""
+    rows = list(csv.DictReader(open(path)))
+    if not rows:
+        return {}
+    col = {k.lower(): k for k in rows[0]}
+    name_c, t0_c, t1_c = col["kernel_name"], col["start_timestamp"], col["end_timestamp"]
+    gy_c, wy_c = col["grid_size_y"], col.get("workgroup_size_y")
+    rows.sort(key=lambda r: int(r[t0_c]))
+    acc, lanes = {}, None
+    for r in rows:
+        name = r[name_c]
+        if "decb_embed_kernel" in name:
+            lanes = int(r[gy_c]) // max(1, int(r[wy_c]) if wy_c else 1)
+        if lanes is None or not ("decb_" in name or "decw_" in name):
+            continue
+        a = acc.setdefault(name[:120], {}).setdefault(lanes, [0, 0])
+        a[0] += 1
+        a[1] += int(r[t1_c]) - int(r[t0_c])
+    out = {}
+    for name, per in acc.items():
+        nbytes = weight_bytes(name, cfg.text)
+        for lanes, (calls, ns) in sorted(per.items()):
+            rec = out.setdefault(name, {})[str(lanes)] = dict(calls=calls, avg_us=ns / calls / 1e3)
+            if nbytes:
+                rec["weight_gb_per_s"] = nbytes / (rec["avg_us"] * 1e-6) / 1e9
+    return out
 
 
 def main():
@@ -124,6 +166,10 @@ def main():
                                                                "read against get prefill_fp8=True")
     ap.add_argument("--sample", action="append", default=[], metavar="T[,K[,P]]",
                     help="also run solo and groups with every stream sampling at temperature T, top_k K (0 = off) and top_p P")
+    ap.add_argument("--wide", action="store_true", help="also run StreamGroup(wide=True) at every lane count of --wide-lanes, read against the "
+                                                        "existing groups of the same run")
+    ap.add_argument("--wide-lanes", default="1,2,4,8,12,16", help="lane counts of the --wide passes")
+    ap.add_argument("--kernel-trace", default=None, help="rocprofv3 kernel_trace CSV of a --kernels-only run: lane-batched kernel averages per lane count")
     ap.add_argument("--kernels-only", action="store_true", help="one short pass per B and nothing else (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 kernel_stats CSV of a --kernels-only run")
     ap.add_argument("--fold", default=None, help="with --kernel-stats: add the kernel averages to this earlier record of the same workload "
@@ -152,12 +198,20 @@ def main():
         stem = "stream_group_prefill_fp4" if args.prefill_fp4 else "stream_group_fp4"
         args.out = os.path.join(root, "profiles", f"{stem}_{args.model}.json")
 
+    wide_lanes = [int(v) for v in args.wide_lanes.split(",")] if args.wide else []
+    if args.wide and (args.llm_fp8 or args.llm_fp4 or settings):
+        ap.error("--wide is bf16 weights and greedy decoding: not with --llm-fp8 / --llm-fp4 / --sample")
+    if args.wide and not args.kernels_only and not args.fold and args.out is None:
+        args.out = os.path.join(root, "profiles", f"stream_group_wide_{args.model}.json")
     cfg = {"2b": C.qwen2_vl_2b, "7b": C.qwen2_vl_7b, "tiny": C.tiny}[args.model]()
     if args.fold:
-        if not args.kernel_stats:
-            ap.error("--fold needs --kernel-stats")
+        if not args.kernel_stats and not args.kernel_trace:
+            ap.error("--fold needs --kernel-stats or --kernel-trace")
         out = json.load(open(args.fold))
-        out["kernel_stats"] = kernel_stats(args.kernel_stats, cfg)
+        if args.kernel_stats:
+            out["kernel_stats"] = kernel_stats(args.kernel_stats, cfg)
+        if args.kernel_trace:
+            out["kernel_avg_by_lanes"] = kernel_trace_by_lanes(args.kernel_trace, cfg)
         with open(args.out or args.fold, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
         return
@@ -240,10 +294,10 @@ def main():
     if args.kernels_only and args.llm_fp4:
         timed(solo_run, 1, False)      # the single-row fp4 kernels in the same trace, beside their lane-batched twins
 
-    def group_passes(m, sample=None):
+    def group_passes(m, sample=None, wide=False):
         groups = {}
-        for B in range(1, args.max_lanes + 1):
-            group = StreamGroup(m._svlm_engine, B, sampling=sample is not None)
+        for B in (wide_lanes if wide else range(1, args.max_lanes + 1)):
+            group = StreamGroup(m._svlm_engine, B, sampling=sample is not None, **(dict(wide=True) if wide else {}))
             rec = timed(lambda kws: S.streaming_inference_group(m, proc, kws, group=group), B, False, sample)
             # the decode steps alone: the batched step graph of the last batch, one chunk's worth of replays per round
             rec["decode_ms_per_chunk"] = replay_decode(next(reversed(group._graphs.values()))[0], group.lanes, args.new_tokens - 1)
@@ -313,6 +367,21 @@ def main():
         if "solo" in out:
             fps_solo = [p["frames_per_sec"] for p in out["solo"]["passes"]]
             out["best"].update(solo_fp4_frames_per_sec=ref, solo_fp4_frames_per_sec_spread=max(fps_solo) - min(fps_solo))
+    if args.wide:
+        # the wide groups of the same model, same process, same run: read against the existing groups above, never against another day's
+        gw = out["group_wide"] = group_passes(model, wide=True)
+        for B, rec in gw.items():
+            if "solo" in out:
+                rec["aggregate_frames_per_sec_vs_solo"] = rec["frames_per_sec"] / ref
+            if B in groups:
+                g = groups[B]
+                rec["decode_step_vs_group"] = rec["decode_us_per_step_median"] / g["decode_us_per_step_median"]
+                rec["decode_step_us_saved_vs_group"] = g["decode_us_per_step_median"] - rec["decode_us_per_step_median"]
+                rec["decode_step_spread_of_both_us"] = rec["decode_us_per_step_spread"] + g["decode_us_per_step_spread"]
+                rec["frames_per_sec_vs_group"] = rec["frames_per_sec"] / g["frames_per_sec"]
+        best = lambda g: max(g, key=lambda B: g[B]["frames_per_sec"])
+        out["best"] = dict(wide_lanes=int(best(gw)), wide_frames_per_sec=gw[best(gw)]["frames_per_sec"],
+                           group_lanes=int(best(groups)), group_frames_per_sec=groups[best(groups)]["frames_per_sec"])
     if settings:
         # every stream draws its tokens: the solo sampled stream and the sampling groups of the same process and run, each read against
         # its greedy counterpart above
@@ -336,6 +405,8 @@ def main():
                     g["surcharge_vs_solo_surcharge"] = g["surcharge_us_per_step_vs_greedy_group"] / rec["solo"]["surcharge_us_per_step"]
     if args.kernel_stats:
         out["kernel_stats"] = kernel_stats(args.kernel_stats, cfg)
+    if args.kernel_trace:
+        out["kernel_avg_by_lanes"] = kernel_trace_by_lanes(args.kernel_trace, cfg)
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
