@@ -545,6 +545,31 @@ int svlm_decb_lm_head_sample_fp8(const void* lanes, const void* samples, int B, 
 int svlm_decb_sample_finish(const void* lanes, const void* samples, int B, const float* logits, int ldl, const int* suppress,
                             const void* ws, int V, int advance_kv, void* stream);
 
+/* ---- stream groups: lane-batched decode attention (csrc/decode_attn.hip; StreamGroup(batched_attn=True)).  The attention of all B lanes
+ * of a batch in ONE split launch and ONE combine launch per layer, where a group otherwise calls svlm_decode_attn_lin once per lane.  The
+ * lane is the third grid dimension of the same kernels; a workgroup takes pool, n_slots, slot_of, state (state[0] = the device length,
+ * one is added), lin, lin_rows and liveness from the lane table, and the rest from a table of B svlm_lane_attn records parallel to it
+ * (record b belongs to lane b).  Lane b's query is row b of q (ldq elements apart), its output row b of out (ldo apart).  Per live lane
+ * the result is BITWISE that of svlm_decode_attn_lin called for the lane alone with max_len = attn_len; a lane that is not live is
+ * skipped (its output row and workspace stay as they are).  Lanes may differ in attn_len, chunk, n_slots, lin_rows and in having linear
+ * planes: each reaches the kernels the single-lane entry picks for it (split for chunk <= 64, else the streaming kernel, with or without
+ * planes; combine over 1, 2 or 4 column parts by its split count), one launch pair per kind present in the batch.
+ * attn_lens / chunks / has_lin: HOST arrays of B ints that repeat the records (and whether the lane has linear planes) for the grids.
+ * The records are trusted (sizes, lin_rows >= attn_len: checked by whoever packs them); a lane whose host entries disagree with its
+ * records is skipped -- its output row stays as it is -- it is not an error the entry can report.
+ * B in 1..16, head_dim 128, Hq / Hkv <= 8, every chunk legal for svlm_decode_attn_lin, ldq a multiple of 8.
+ * replaces: qwen2/language_forward.py:55-63,107-108,148 on the decode steps of a group (as svlm_decode_attn_lin). */
+typedef struct svlm_lane_attn {
+  const void* rope_cs;     /* the lane's cos / sin table, at least attn_len rows of D bf16 */
+  const int* lin_len_dev;  /* lin_state[2] of the lane's linear planes (svlm_decode_attn_lin), or NULL: no planes are used */
+  void* ws;                /* the lane's workspace, >= svlm_decode_attn_ws_bytes(Hq, attn_len, chunk) */
+  int attn_len;            /* the max_len argument of the single-lane call */
+  int chunk;
+} svlm_lane_attn;          /* 32 bytes */
+int svlm_decb_attn_max_lanes(void); /* [host] 16 */
+int svlm_decb_attn(const void* lanes, const void* attn, int B, const void* q, int ldq, void* out, int ldo, int layer, int Hq, int Hkv,
+                   int D, float scale, const int* attn_lens, const int* chunks, const int* has_lin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

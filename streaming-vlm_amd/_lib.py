@@ -116,6 +116,8 @@ SIGNATURES = {
     "svlm_decb_lm_head_sample": (_i, [_p, _p, _i, _p, _i, _p, _f, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_decb_lm_head_sample_fp8": (_i, [_p, _p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p]),
     "svlm_decb_sample_finish": (_i, [_p, _p, _i, _p, _i, _p, _p, _i, _i, _p]),
+    "svlm_decb_attn_max_lanes": (_i, []),
+    "svlm_decb_attn": (_i, [_p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
 }
 
 _lib = None

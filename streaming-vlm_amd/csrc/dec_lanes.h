@@ -31,6 +31,17 @@ struct svlm_lane_sample {          // mirror of include/svlm.h
 static_assert(sizeof(svlm_lane_sample) == 24, "svlm_lane_sample layout (include/svlm.h)");
 enum { SVLM_SAMPLE_GREEDY = 0, SVLM_SAMPLE_GUMBEL = 1, SVLM_SAMPLE_FILTERED = 2, SVLM_SAMPLE_NUCLEUS = 3 };
 
+// The attention record of a lane, in a table of its own parallel to the lane table (svlm_decb_attn, decode_attn.hip): what the
+// single-stream decode attention takes as arguments and the lane record does not hold.
+struct svlm_lane_attn {            // mirror of include/svlm.h
+  const bf16_t* rope_cs;           // the lane's cos / sin table [>= attn_len][D]
+  const int* lin_len_dev;          // lin_state {rows rotated, fresh rows follow} of the lane's linear planes, or null (no planes)
+  float* ws;                       // the lane's decode workspace, svlm_decode_attn_ws_bytes(Hq, attn_len, chunk)
+  int attn_len;                    // max_len of the single-lane call: the split count is ceil(attn_len / chunk)
+  int chunk;                       // keys per workgroup
+};
+static_assert(sizeof(svlm_lane_attn) == 32, "svlm_lane_attn layout (include/svlm.h)");
+
 // host side, defined in decode_batch.hip: the candidate workspace stride, and the launches of the embed and finish kernels without the
 // B <= 4 check of their entries (shared with the wide entries of decode_wide.hip)
 extern "C" long long svlm_decb_lm_head_ws_stride(int V);

@@ -17,6 +17,7 @@
 // the four waves merge through LDS; a second small kernel merges the splits with the splits
 // spread over waves and the loads unrolled.
 #include "common.h"
+#include "dec_lanes.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -57,19 +58,76 @@ extern "C" int svlm_diag_set_da_stamps(void* p) {
 }
 #define DA_STAMP(wg, i)                                                                        \
   do {                                                                                         \
-    if (threadIdx.x == 0 && da_stamps != nullptr) da_stamps[(size_t)(wg) * 8 + (i)] = wall_clock64(); \
+    if ((wg) >= 0 && threadIdx.x == 0 && da_stamps != nullptr) da_stamps[(size_t)(wg) * 8 + (i)] = wall_clock64(); \
   } while (0)
 #else
 #define DA_STAMP(wg, i) do { } while (0)
 #endif
 
-template <int G>
+// ---- the lane-batched form of the three kernels below (svlm_decb_attn): LANES = true adds the lane as blockIdx.z, and a workgroup
+// takes what the single-lane kernel gets as kernel arguments from the lane table and the attention table instead.  Everything behind
+// that prologue is the ONE body both forms compile.  A lane reaches the kernel svlm_decode_attn_lin would launch for it alone -- its
+// class -- and a launch serves one class: workgroups of lanes that are not live, of another class, or past their lane's own split count
+// exit before they touch memory the lane owns.
+enum { DA_CLS_SPLIT = 0, DA_CLS_STREAM = 1, DA_CLS_STREAM_LIN = 2 };
+static inline __host__ __device__ int da_split_class(int chunk, bool has_lin) {
+  return chunk <= 16 * DA_MAX_STEPS ? DA_CLS_SPLIT : (has_lin ? DA_CLS_STREAM_LIN : DA_CLS_STREAM);
+}
+static inline __host__ __device__ int da_combine_ds(int ns_max) { return ns_max > 192 ? 4 : (ns_max > 64 ? 2 : 1); }
+
+// The tables reach a LANES kernel as a trailing parameter pack (lanes, attn, ld, layer) that is EMPTY in the single-lane form, whose
+// kernel arguments -- and with them its code object -- are those it had before the lane-batched form existed.
+struct DaLaneTab {
+  const svlm_lane* lanes;
+  const svlm_lane_attn* attn;
+  int ld;                          // row stride of the group's q (split) / out (combine) buffer, elements
+  int layer;
+};
+struct DaLaneArgs {
+  const bf16_t *k_planes, *v_planes, *rope_cs, *k_lin, *v_lin;
+  const int *slot_of, *len_dev, *lin_len_dev;
+  float *ws_m, *ws_l, *ws_acc;
+  int n_slots, chunk, max_len, lin_rows, ns;
+  bool live, has_lin;
+};
+__device__ __forceinline__ DaLaneArgs da_lane_args(const svlm_lane* __restrict__ lanes, const svlm_lane_attn* __restrict__ attn, int layer,
+                                                   int Hq, int Hkv) {
+  const svlm_lane& L = lanes[blockIdx.z];
+  const svlm_lane_attn& A = attn[blockIdx.z];
+  DaLaneArgs a;
+  a.live = lane_live(L);
+  a.has_lin = L.lin != nullptr && A.lin_len_dev != nullptr;
+  a.n_slots = L.n_slots; a.chunk = A.chunk; a.max_len = A.attn_len; a.lin_rows = L.lin_rows;
+  a.ns = (A.attn_len + A.chunk - 1) / A.chunk;
+  const size_t plane = (size_t)Hkv * L.n_slots * DA_D, lplane = (size_t)Hkv * L.lin_rows * DA_D;      // as decw_qkv_kernel addresses them
+  a.k_planes = L.pool + (size_t)layer * 2 * plane;
+  a.v_planes = a.k_planes + plane;
+  a.k_lin = a.has_lin ? L.lin + (size_t)layer * 2 * lplane : nullptr;
+  a.v_lin = a.has_lin ? a.k_lin + lplane : nullptr;
+  a.lin_len_dev = a.has_lin ? A.lin_len_dev : nullptr;
+  a.slot_of = L.slot_of; a.len_dev = L.state; a.rope_cs = A.rope_cs;
+  a.ws_m = A.ws;
+  a.ws_l = a.ws_m + (size_t)a.ns * Hq;
+  a.ws_acc = a.ws_l + (size_t)a.ns * Hq;
+  return a;
+}
+
+template <int G, bool LANES = false, class... TAB>
 __global__ __launch_bounds__(256) void decode_attn_split_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_planes, const bf16_t* __restrict__ v_planes,
     const int* __restrict__ slot_of, const bf16_t* __restrict__ rope_cs, const int* __restrict__ len_dev, int len_add,
     float* __restrict__ ws_m, float* __restrict__ ws_l, float* __restrict__ ws_acc, int Hq, int Hkv, int n_slots,
     int chunk, float scale, int max_len, const bf16_t* __restrict__ k_lin, const bf16_t* __restrict__ v_lin, int lin_rows,
-    const int* __restrict__ lin_len_dev) {
+    const int* __restrict__ lin_len_dev, TAB... tab) {
+  if constexpr (LANES) {         // (q: the group's buffer, lane b's row at b * t.ld; Hq, Hkv, scale: the launch's; the length is state[0] + 1)
+    const DaLaneTab t{tab...};
+    const DaLaneArgs a = da_lane_args(t.lanes, t.attn, t.layer, Hq, Hkv);
+    if (!a.live || da_split_class(a.chunk, a.has_lin) != DA_CLS_SPLIT || (int)blockIdx.x >= a.ns) return;      // workgroup-uniform
+    q += (size_t)blockIdx.z * t.ld;
+    k_planes = a.k_planes; v_planes = a.v_planes; slot_of = a.slot_of; rope_cs = a.rope_cs; len_dev = a.len_dev; len_add = 1;
+    ws_m = a.ws_m; ws_l = a.ws_l; ws_acc = a.ws_acc; n_slots = a.n_slots; chunk = a.chunk; max_len = a.max_len;
+    k_lin = a.k_lin; v_lin = a.v_lin; lin_rows = a.lin_rows; lin_len_dev = a.lin_len_dev;
+  }
   __shared__ __attribute__((aligned(16))) unsigned char lds[64 * DA_KLD * 2 + 64 * DA_VLD * 2 + 16 * DA_KLD * 2 + 512];
   bf16_t* Ks = reinterpret_cast<bf16_t*>(lds);
   bf16_t* Vs = Ks + 64 * DA_KLD;
@@ -82,7 +140,7 @@ __global__ __launch_bounds__(256) void decode_attn_split_kernel(
   const int kvh = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int srow = tid >> 4, c = tid & 15;      // staging: 16 lanes per 256-B row
-  const int wg_id = blockIdx.y * gridDim.x + blockIdx.x;
+  const int wg_id = LANES ? -1 : blockIdx.y * gridDim.x + blockIdx.x;      // (the stamps stay with the single-lane form)
   (void)wg_id;
   DA_STAMP(wg_id, 0);
   const bool upper = c >= 8;
@@ -493,13 +551,24 @@ struct DaTile {
   u32x4_t k[4], cs[4], v[4];     // K pieces ks = 0..3; cos pieces 0,1 and sin pieces 0,1; V rows 4 i + (lane >> 4), chunk lane & 15
 };
 
-template <int G, int DIAG = 0, bool WLIN = false>       // WLIN: launched with linear planes (below); DIAG bits (diagnostic build only): 1 = no cos/sin loads, no rotation; 2 = loads only, no arithmetic at all; 4 = cos/sin rows from a 16 KB table
+template <int G, int DIAG = 0, bool WLIN = false, bool LANES = false, class... TAB>       // WLIN: launched with linear planes (below); DIAG bits (diagnostic build only): 1 = no cos/sin loads, no rotation; 2 = loads only, no arithmetic at all; 4 = cos/sin rows from a 16 KB table
 __global__ __launch_bounds__(256, 2) void decode_attn_stream_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k_planes, const bf16_t* __restrict__ v_planes,
     const int* __restrict__ slot_of, const bf16_t* __restrict__ rope_cs, const int* __restrict__ len_dev, int len_add,
     float* __restrict__ ws_m, float* __restrict__ ws_l, float* __restrict__ ws_acc, int Hq, int Hkv, int n_slots,
     int chunk, float scale, int max_len, const bf16_t* __restrict__ k_lin, const bf16_t* __restrict__ v_lin, int lin_rows,
-    const int* __restrict__ lin_len_dev) {
+    const int* __restrict__ lin_len_dev, TAB... tab) {
+  int n_ranges = gridDim.x;
+  if constexpr (LANES) {         // (q: the group's buffer, lane b's row at b * t.ld; Hq, Hkv, scale: the launch's; the length is state[0] + 1)
+    const DaLaneTab t{tab...};
+    const DaLaneArgs a = da_lane_args(t.lanes, t.attn, t.layer, Hq, Hkv);
+    if (!a.live || da_split_class(a.chunk, a.has_lin) != (WLIN ? DA_CLS_STREAM_LIN : DA_CLS_STREAM) || (int)blockIdx.x >= a.ns) return;      // workgroup-uniform
+    q += (size_t)blockIdx.z * t.ld;
+    k_planes = a.k_planes; v_planes = a.v_planes; slot_of = a.slot_of; rope_cs = a.rope_cs; len_dev = a.len_dev; len_add = 1;
+    ws_m = a.ws_m; ws_l = a.ws_l; ws_acc = a.ws_acc; n_slots = a.n_slots; chunk = a.chunk; max_len = a.max_len;
+    k_lin = a.k_lin; v_lin = a.v_lin; lin_rows = a.lin_rows; lin_len_dev = a.lin_len_dev;
+    n_ranges = a.ns;
+  }
   // LDS: [4][16][DA_OLD] fp32 merge buffer (33 KB), whose first 18 KB double as the four waves' V slabs during the loop; Q block; m / l
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 16 * DA_OLD * 4 + 16 * DA_KLD * 2 + 512];
   float* Om = reinterpret_cast<float*>(lds);
@@ -508,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_stream_kernel(
   float* Lm = Mm + 64;
 
   // the LAST key range is dispatched FIRST: it is the one that holds the rows appended since the prefill (pool path below, slower per tile)
-  const int sp = gridDim.x - 1 - blockIdx.x;
+  const int sp = n_ranges - 1 - blockIdx.x;
   const int start = sp * chunk;
   const int kvh = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -770,17 +839,25 @@ __global__ __launch_bounds__(256, 2) void decode_attn_stream_kernel(
 #ifndef DA_CB
 #define DA_CB 12
 #endif
-template <int NW, int DS>
+template <int NW, int DS, bool LANES = false, class... TAB>
 __global__ __launch_bounds__(NW * 64) void decode_attn_combine_kernel(const float* __restrict__ ws_m, const float* __restrict__ ws_l,
                                                                       const float* __restrict__ ws_acc, const int* __restrict__ len_dev,
-                                                                      int len_add, bf16_t* __restrict__ out, int Hq, int chunk, int ns_max) {
+                                                                      int len_add, bf16_t* __restrict__ out, int Hq, int chunk, int ns_max,
+                                                                      TAB... tab) {
+  if constexpr (LANES) {         // (out: the group's buffer, lane b's row at b * t.ld; a launch serves the lanes whose split count takes this DS)
+    const DaLaneTab t{tab...};
+    const DaLaneArgs a = da_lane_args(t.lanes, t.attn, 0, Hq, 1);
+    if (!a.live || da_combine_ds(a.ns) != DS) return;        // workgroup-uniform
+    out += (size_t)blockIdx.z * t.ld;
+    ws_m = a.ws_m; ws_l = a.ws_l; ws_acc = a.ws_acc; len_dev = a.len_dev; len_add = 1; chunk = a.chunk; ns_max = a.ns;
+  }
   constexpr int CW = 64 / DS;            // lanes across the workgroup's columns (2 columns each)
   constexpr int SUB = DS;                // split sub-slots per wave
   constexpr int STRIDE = NW * SUB;       // splits covered per step of u
   const int hq = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int cl = lane % CW, sub = lane / CW;
-  const int cwg = 4096 + blockIdx.y * gridDim.x + blockIdx.x;      // (stamp rows of the combine sit behind the split's)
+  const int cwg = LANES ? -1 : 4096 + blockIdx.y * gridDim.x + blockIdx.x;      // (stamp rows of the combine sit behind the split's)
   (void)cwg;
   DA_STAMP(cwg, 0);
   const int col = blockIdx.y * (DA_D / DS) + 2 * cl;
@@ -980,4 +1057,74 @@ extern "C" int svlm_decode_attn_ropeload(const void* q, const void* k_planes, co
                                          int Hq, int Hkv, int D, int n_slots, int max_len, int chunk, float scale, void* stream) {
   return svlm_decode_attn_lin(q, k_planes, v_planes, slot_of, rope_cs, len_dev, len_add, nullptr, nullptr, 0, nullptr, out, ws, Hq, Hkv, D,
                               n_slots, max_len, chunk, scale, stream);
+}
+
+// ---- stream groups: the decode attention of all B lanes of a batch in one split launch and one combine launch (per class present)
+// The LANES = true forms of the kernels above, grid z = the lane.  Per live lane exactly what svlm_decode_attn_lin computes for the lane
+// alone with (q row b, the lane's planes of `layer`, slot_of, rope_cs, len_dev = state, len_add = 1, its linear planes, out row b, ws,
+// n_slots, max_len = attn_len, chunk): same kernel, same body, same split count, same workspace layout -- the same bits.  A lane that is
+// not live is skipped: its output row and its workspace stay as they are.
+// The host arrays (B entries each) repeat what the device records hold, for the grids and the classes: attn_len and chunk of every lane
+// and whether it has linear planes.  A batch normally has one class (two launches); lanes on either side of a threshold get a launch
+// pair per class, in which the workgroups of the other lanes exit at once.
+// The kernels take a lane's class from its device records, the launcher from the host arrays, and nothing here can compare the two: a
+// lane whose host entries disagree with its records finds no launch of its class and is SKIPPED (output row left stale), it does not
+// fault.  Nor can the entry check what svlm_decode_attn_lin checks on its arguments (lin_rows >= attn_len, the table and workspace
+// sizes): the records are trusted as svlm_lane records are; ops.lane_attn_record / ops.lane_record validate them where they are packed.
+#define DAB_MAX_LANES 16
+extern "C" int svlm_decb_attn_max_lanes(void) { return DAB_MAX_LANES; }
+
+template <int G>
+static void launch_split_lanes(int cls, dim3 grid, hipStream_t st, const svlm_lane* lanes, const svlm_lane_attn* attn, const bf16_t* q, int ldq,
+                               int layer, int Hq, int Hkv, float scale) {
+#define DAB_ARGS q, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, nullptr, nullptr, Hq, Hkv, 0, 0, scale, 0, nullptr, nullptr, 0, nullptr, lanes, attn, ldq, layer
+  if (cls == DA_CLS_STREAM_LIN) decode_attn_stream_kernel<G, 0, true, true><<<grid, 256, 0, st>>>(DAB_ARGS);
+  else if (cls == DA_CLS_STREAM) decode_attn_stream_kernel<G, 0, false, true><<<grid, 256, 0, st>>>(DAB_ARGS);
+  else decode_attn_split_kernel<G, true><<<grid, 256, 0, st>>>(DAB_ARGS);
+#undef DAB_ARGS
+}
+
+extern "C" int svlm_decb_attn(const void* lanes, const void* attn, int B, const void* q, int ldq, void* out, int ldo, int layer, int Hq,
+                              int Hkv, int D, float scale, const int* attn_lens, const int* chunks, const int* has_lin, void* stream) {
+  SVLM_CHECK_ARG(lanes != nullptr && attn != nullptr && B >= 1 && B <= DAB_MAX_LANES, "svlm_decb_attn: bad tables or B=%d (1..%d lanes)", B,
+                 DAB_MAX_LANES);
+  SVLM_CHECK_ARG(q != nullptr && out != nullptr && attn_lens != nullptr && chunks != nullptr && has_lin != nullptr && layer >= 0,
+                 "svlm_decb_attn: null q / out / host arrays or layer=%d", layer);
+  SVLM_CHECK_ARG(D == DA_D, "svlm_decb_attn: head_dim %d unsupported (128 only)", D);
+  SVLM_CHECK_ARG(Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq / Hkv <= DA_GMAX, "svlm_decb_attn: Hq=%d Hkv=%d (group must be <= %d)", Hq, Hkv, DA_GMAX);
+  SVLM_CHECK_ARG(ldq >= Hq * DA_D && ldq % 8 == 0 && ldo >= Hq * DA_D, "svlm_decb_attn: ldq=%d ldo=%d for rows of %d (ldq a multiple of 8)", ldq,
+                 ldo, Hq * DA_D);
+  int ns_split[3] = {0, 0, 0}, n_ds[3] = {0, 0, 0};       // largest split count per split class; lanes per combine DS (1, 2, 4)
+  for (int b = 0; b < B; ++b) {
+    const int chunk = chunks[b], len = attn_lens[b];
+    SVLM_CHECK_ARG(chunk > 0 && len > 0 && ((chunk % 16 == 0 && chunk <= 16 * DA_MAX_STEPS) || (chunk % 64 == 0 && chunk <= DA_LONG_MAX)),
+                   "svlm_decb_attn: lane %d: attn_len=%d chunk=%d (chunk a multiple of 16 up to %d or a multiple of 64 up to %d)", b, len, chunk,
+                   16 * DA_MAX_STEPS, DA_LONG_MAX);
+    const int ns = (len + chunk - 1) / chunk, cls = da_split_class(chunk, has_lin[b] != 0), ds = da_combine_ds(ns);
+    ns_split[cls] = ns > ns_split[cls] ? ns : ns_split[cls];
+    ++n_ds[ds >> 1];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const svlm_lane* lt = (const svlm_lane*)lanes;
+  const svlm_lane_attn* at = (const svlm_lane_attn*)attn;
+  for (int cls = 0; cls < 3; ++cls) {
+    if (ns_split[cls] == 0) continue;
+    const dim3 grid(ns_split[cls], Hkv, B);
+#define SVLM_DAB_CASE(GG) \
+  case GG: launch_split_lanes<GG>(cls, grid, st, lt, at, (const bf16_t*)q, ldq, layer, Hq, Hkv, scale); break;
+    switch (Hq / Hkv) {
+      SVLM_DAB_CASE(1) SVLM_DAB_CASE(2) SVLM_DAB_CASE(3) SVLM_DAB_CASE(4) SVLM_DAB_CASE(5) SVLM_DAB_CASE(6) SVLM_DAB_CASE(7) SVLM_DAB_CASE(8)
+    }
+#undef SVLM_DAB_CASE
+    int rc = svlm_check_launch("svlm_decb_attn(split)");
+    if (rc) return rc;
+  }
+  bf16_t* o = (bf16_t*)out;
+  if (n_ds[0])
+    decode_attn_combine_kernel<4, 1, true><<<dim3(Hq, 1, B), 256, 0, st>>>(nullptr, nullptr, nullptr, nullptr, 1, o, Hq, 0, 0, lt, at, ldo, 0);
+  if (n_ds[1])
+    decode_attn_combine_kernel<4, 2, true><<<dim3(Hq, 2, B), 256, 0, st>>>(nullptr, nullptr, nullptr, nullptr, 1, o, Hq, 0, 0, lt, at, ldo, 0);
+  if (n_ds[2])
+    decode_attn_combine_kernel<16, 4, true><<<dim3(Hq, 4, B), 1024, 0, st>>>(nullptr, nullptr, nullptr, nullptr, 1, o, Hq, 0, 0, lt, at, ldo, 0);
+  return svlm_check_launch("svlm_decb_attn(combine)");
 }

@@ -74,7 +74,7 @@ class StreamGroupError(RuntimeError):
 
 
 def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Optional[int] = None, group=None, sampling: bool = False,
-                              wide: bool = False, **common_kw) -> List:
+                              wide: bool = False, batched_attn: bool = False, **common_kw) -> List:
     """Run `len(streams)` streams on ONE GPU through a stream group: each entry of `streams` holds the per-stream keyword arguments of
     `streaming_inference` (video_path, query, previous_text, duration, ...), `common_kw` the shared ones.  Every stream runs the
     unchanged `streaming_inference` loop in its own host thread against its lane's model object; the lanes' generate() calls meet in
@@ -85,15 +85,18 @@ def streaming_inference_group(model, processor, streams: List[dict], n_lanes: Op
     `StreamGroup(..., sampling=True)` and every stream may carry its own `do_sample / temperature / top_k / top_p / generator` -- each
     lane then produces the tokens of that stream run alone on a fresh model with the same generator seed (an existing `group` passed in
     keeps the setting it was built with).  `wide=True` builds `StreamGroup(..., wide=True)`: up to 16 lanes on the MFMA decode kernels
-    (bf16 weights, greedy; `n_lanes` still defaults to min(3, streams)).  Strict-causal (no look-ahead ViT).  Returns the per-stream response
+    (bf16 weights, greedy; `n_lanes` still defaults to min(3, streams)).  `batched_attn=True` builds `StreamGroup(..., batched_attn=True)`:
+    the decode attention of all lanes in one launch pair per layer (same tokens; combines with every other option).  Strict-causal (no look-ahead ViT).  Returns the per-stream response
     lists in the order of `streams`; if a stream raised, the others still run to their end and a `StreamGroupError` naming the first
     failed stream's index is raised afterwards."""
     import threading
     from .driver import streaming_inference
     from .stream_group import DEFAULT_LANES, StreamGroup
     if group is None:
+        # an option that is off is not passed: stand-ins for StreamGroup that older tests substitute do not know the keyword
+        opt = {"batched_attn": True} if batched_attn else {}
         group = StreamGroup(model._svlm_engine, min(DEFAULT_LANES, len(streams)) if n_lanes is None else n_lanes, sampling=sampling,
-                            wide=wide)
+                            wide=wide, **opt)
     results: List = [None] * len(streams)
     errors = {}
     lock = threading.Lock()

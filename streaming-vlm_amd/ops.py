@@ -799,6 +799,70 @@ class HipOps:
         self._check(self.lib.svlm_decb_sample_finish(_ptr(lanes), _ptr(samples), B, _ptr(logits), ldl, _ptr(suppress), _ptr(ws), int(V),
                                                int(advance_kv), _stream()), "svlm_decb_sample_finish")
 
+    # ------------------------------------------------------------------ lane-batched decode attention (csrc/decode_attn.hip)
+    # per-lane attention records (svlm_lane_attn, include/svlm.h): a table parallel to the lane table
+    ATTN_WORDS = 4          # int64 words of one svlm_lane_attn record
+
+    @staticmethod
+    def decode_chunk_legal(chunk):
+        """The chunk rule of svlm_decode_attn_lin: a multiple of 16 up to 64 (split kernel) or a multiple of 64 up to 512 (streaming)."""
+        chunk = int(chunk)
+        return chunk > 0 and ((chunk % 16 == 0 and chunk <= 64) or (chunk % 64 == 0 and chunk <= 512))
+
+    def lane_attn_record(self, rope_cs, lin_state, ws, attn_len, chunk, Hq, slot_of=None, lin=None):
+        """One svlm_lane_attn record as int64[ATTN_WORDS] on the host: what `decode_attn` takes per call and the lane record does not
+        hold -- the rope table, the lin_state of the lane's linear planes (None: no planes are used), the decode workspace, and
+        `attn_len` (the max_len argument) and `chunk` of the call.  Checked here as `decode_attn` checks them (the kernels trust it);
+        `slot_of` / `lin`: the lane record's, when given checked against attn_len too."""
+        import numpy as np
+        attn_len, chunk = int(attn_len), int(chunk)
+        _req(rope_cs, BF16, "lane_attn.rope_cs", 2); _req(ws, torch.float32, "lane_attn.ws", 1)
+        if not self.decode_chunk_legal(chunk):
+            raise _lib.SvlmError(f"lane_attn_record: chunk={chunk} must be a multiple of 16 up to 64 or a multiple of 64 up to 512")
+        if not (0 < attn_len <= rope_cs.shape[0] and rope_cs.shape[1] == 128 and rope_cs.is_contiguous()):
+            raise _lib.SvlmError(f"lane_attn_record: attn_len={attn_len} for a rope table {tuple(rope_cs.shape)} (head_dim 128)")
+        need = self.lib.svlm_decode_attn_ws_bytes(int(Hq), attn_len, chunk)
+        if need < 0 or ws.numel() * 4 < need:
+            raise _lib.SvlmError(f"lane_attn_record: workspace of {ws.numel() * 4} B, {need} needed (Hq={Hq} attn_len={attn_len} chunk={chunk})")
+        if lin_state is not None:
+            _req(lin_state, torch.int32, "lane_attn.lin_state", 1)
+            assert lin_state.numel() == 2, "lin_state = {rows rotated, appended rows follow}"
+        if slot_of is not None:
+            assert attn_len <= slot_of.numel(), (attn_len, slot_of.numel())
+        if lin is not None:
+            assert lin.shape[3] % 16 == 0 and lin.shape[3] >= attn_len, (lin.shape[3], attn_len)
+        rec = np.zeros(HipOps.ATTN_WORDS, dtype=np.int64)
+        rec[:3] = [_ptr(rope_cs), _ptr(lin_state), _ptr(ws)]
+        rec[3:4].view(np.int32)[:] = [attn_len, chunk]
+        return rec
+
+    def decb_attn_max_lanes(self):
+        return int(self.lib.svlm_decb_attn_max_lanes())
+
+    def decb_attn(self, lanes, attn_table, B, q, out, layer, Hq, scale, attn_lens, chunks, has_lin, Hkv, D=128):
+        """The decode attention of the B lanes of a batch in one split + one combine launch: per live lane the bits of `decode_attn` for
+        the lane alone (q row b -> out row b; everything else from lane-table row b and attention-table row b).  attn_lens / chunks /
+        has_lin: per lane, on the host, what the records hold (has_lin: the lane record has planes AND its attention record a lin_state)."""
+        import ctypes
+        if lanes is None or attn_table is None:
+            raise _lib.SvlmError("decb_attn: the lane table and the attention table are required")
+        _req(lanes, torch.int64, "decb_attn.lanes", 2); _req(attn_table, torch.int64, "decb_attn.attn_table", 2)
+        if not (1 <= B <= 16 and lanes.shape[0] >= B and lanes.shape[1] == self.LANE_WORDS and lanes.is_contiguous()):
+            raise _lib.SvlmError(f"decb_attn: lane table {tuple(lanes.shape)} for B={B} (1..16 lanes of {self.LANE_WORDS} words)")
+        if not (attn_table.shape[0] >= B and attn_table.shape[1] == self.ATTN_WORDS and attn_table.is_contiguous()):
+            raise _lib.SvlmError(f"decb_attn: attention table {tuple(attn_table.shape)} for B={B} (records of {self.ATTN_WORDS} words)")
+        if not (len(attn_lens) == len(chunks) == len(has_lin) == B):
+            raise _lib.SvlmError(f"decb_attn: {len(attn_lens)} / {len(chunks)} / {len(has_lin)} host entries for B={B}")
+        for b in range(B):
+            if not self.decode_chunk_legal(chunks[b]) or int(attn_lens[b]) <= 0:
+                raise _lib.SvlmError(f"decb_attn: lane {b}: attn_len={attn_lens[b]} chunk={chunks[b]} (chunk a multiple of 16 up to 64 or a "
+                                     "multiple of 64 up to 512)")
+        ldq, ldo = self._rows(q, B, Hq * D, "decb_attn.q"), self._rows(out, B, Hq * D, "decb_attn.out")
+        arr = (ctypes.c_int * (3 * B))(*[int(v) for v in attn_lens], *[int(v) for v in chunks], *[int(bool(v)) for v in has_lin])
+        base = ctypes.addressof(arr)
+        self._check(self.lib.svlm_decb_attn(_ptr(lanes), _ptr(attn_table), B, _ptr(q), ldq, _ptr(out), ldo, int(layer), Hq, Hkv, D, float(scale),
+                                            base, base + 4 * B, base + 8 * B, _stream()), "svlm_decb_attn")
+
     # ------------------------------------------------------------------ wide lane-batched decode step (csrc/decode_wide.hip)
     # The decb_* weight kernels as skinny GEMMs on the MFMA, for 1..16 lanes: same lane table, same operands, same workspace.
     def decw_max_lanes(self):

@@ -13,6 +13,13 @@ everything a stream owns: KV pool, positions, rope table, sampling state, evicti
 lane; per lane the tokens, cache length and logical order are EXACTLY those of the stream run alone (the batched kernels are bitwise
 the single-row ones per lane, and the decode attention is the unchanged single-stream kernel, launched once per lane).
 
+Batched attention.  `StreamGroup(..., batched_attn=True)` replaces those per-lane launches -- `2 * B * n_layers` per step -- by one
+`decb_attn` per layer (csrc/decode_attn.hip, svlm_decb_attn: the same kernels with the lane as a third grid dimension, one split and one
+combine launch for all lanes).  The group keeps a table of `svlm_lane_attn` records parallel to the lane table (rope table, lin_state,
+workspace, and the `attn_len` / `decode_chunk` the lane's `generate_begin` picked for this call), rewritten at the start of every
+`generate()`.  Per lane the attention is bitwise the single-stream kernel's, so the flag changes no token; it combines with `wide`,
+`sampling` and fp8 / fp4 engines.  An ops backend without `decb_attn` is refused with a ValueError that names `batched_attn=True`.
+
 Token choice.  By default a group is greedy.  `StreamGroup(..., sampling=True)` batches the reference's default token choice as well:
 every lane's request carries its own `do_sample / temperature / top_k / top_p / generator`, and one batch may mix greedy, plain
 temperature, top-k (with or without top-p) and top-p alone.  `generate_begin` draws a lane's first token with the single-row kernels and
@@ -62,6 +69,8 @@ DEFAULT_LANES = 3
 # a wide group (wide=True): one lane per column of the 16-wide MFMA tile (csrc/decode_wide.hip, svlm_decw_max_lanes)
 MAX_LANES_WIDE = 16
 WIDE_GROUP_OPS = ("decw_embed", "decw_qkv", "decw_gemv", "decw_gate_up", "decw_lm_head", "decw_argmax_finish")
+# ... and a group with batched_attn=True (csrc/decode_attn.hip, svlm_decb_attn)
+ATTN_GROUP_OPS = ("decb_attn", "lane_attn_record")
 # ops entry points a group on an llm_fp8 engine needs (csrc/decode_batch_fp8.hip)
 FP8_GROUP_OPS = ("decb_qkv_fp8", "decb_gate_up_fp8", "decb_gemv_fp8", "decb_lm_head_fp8")
 # ... and on an llm_fp4 engine (csrc/decode_batch_fp4.hip; the lm_head of an fp4 engine is e4m3)
@@ -179,7 +188,7 @@ class LaneModel:
 
 
 class StreamGroup:
-    def __init__(self, engine: SvlmEngine, n_lanes: int = 2, sampling: bool = False, wide: bool = False):
+    def __init__(self, engine: SvlmEngine, n_lanes: int = 2, sampling: bool = False, wide: bool = False, batched_attn: bool = False):
         max_lanes = MAX_LANES_WIDE if wide else MAX_LANES
         if not 1 <= int(n_lanes) <= max_lanes:
             raise ValueError(f"n_lanes={n_lanes} outside [1, {max_lanes}]" + (" (wide=True)" if wide else ""))
@@ -210,12 +219,18 @@ class StreamGroup:
             if sampling and not hasattr(engine.ops, "decb_lm_head_sample_fp8"):
                 raise ValueError(f"stream group: sampling=True on an llm_fp4=True engine needs an ops backend with the lane-batched fp8 "
                                  f"sampling head; {type(engine.ops).__name__} lacks decb_lm_head_sample_fp8")
+        if batched_attn:
+            missing = [m for m in ATTN_GROUP_OPS if not hasattr(getattr(engine, "ops", None), m)]
+            if missing:
+                raise ValueError(f"stream group: batched_attn=True needs an ops backend with the lane-batched attention entry point; "
+                                 f"{type(getattr(engine, 'ops', None)).__name__} lacks {missing}")
         if getattr(engine, "decode_tail", False):
             raise ValueError("stream group: decode_tail=True engines are not supported (the persistent layer tail is single-row)")
         self.engine = engine
         self.n_lanes = int(n_lanes)
         self.sampling = bool(sampling)
         self.wide = bool(wide)
+        self.batched_attn = bool(batched_attn)
         tc, dev, o = engine.cfg.text, engine.device, engine.ops
         self.lanes: List[SvlmEngine] = [engine] + [
             SvlmEngine(engine.cfg, None, dev, ops=o, max_len=engine.max_len, max_new_tokens=engine.max_new, decode_chunk=engine._fixed_chunk,
@@ -253,6 +268,15 @@ class StreamGroup:
             self._samples_host = torch.zeros((B, o.SAMPLE_WORDS), dtype=torch.int64)
             if dev.type == "cuda":
                 self._samples_host = self._samples_host.pin_memory()
+        # the attention table (svlm_lane_attn records), parallel to the lane table: row j holds the rope table, lin_state, workspace and
+        # the (attn_len, chunk) lane-table row j's generate() call picked; `_attn_host_args` keeps the same per lane for the launcher
+        self.attn_table = self._attn_table_host = None
+        self._attn_host_args = ([], [], [])
+        if self.batched_attn:
+            self.attn_table = torch.zeros((B, o.ATTN_WORDS), dtype=torch.int64, device=dev)
+            self._attn_table_host = torch.zeros((B, o.ATTN_WORDS), dtype=torch.int64)
+            if dev.type == "cuda":
+                self._attn_table_host = self._attn_table_host.pin_memory()
         if self.wide and dev.type == "cuda" and hasattr(o, "decw_reserve_lds"):
             o.decw_reserve_lds()                 # (before any step is captured into a graph)
         self._graphs = {}
@@ -285,6 +309,29 @@ class StreamGroup:
         self._samples_host[row].copy_(torch.from_numpy(rec))
         self.samples[row].copy_(self._samples_host[row], non_blocking=True)
 
+    def _attn_record(self, lane: SvlmEngine, cache):
+        """The lane's svlm_lane_attn record from what its `generate_begin` left: the rope table, the workspace, `_attn_len`, `decode_chunk`."""
+        lin = cache.lin_args() if hasattr(cache, "lin_args") else None
+        return self.engine.ops.lane_attn_record(lane.rope_cs, None if lin is None else lin[1], lane.d_ws, lane._attn_len, lane.decode_chunk,
+                                                self.engine.cfg.text.num_heads, slot_of=cache.slot_of_dev, lin=None if lin is None else lin[0])
+
+    def _write_attn_row(self, row: int, rec: np.ndarray):
+        self._attn_table_host[row].copy_(torch.from_numpy(rec))
+        self.attn_table[row].copy_(self._attn_table_host[row], non_blocking=True)
+
+    def _attn(self, act, tab, B, li, scale):
+        """The decode attention of layer `li` for the batch: the single-stream kernel pair once per lane on the same stream (no forked
+        branches), or with `batched_attn` all lanes in one `decb_attn` (one split and one combine launch)."""
+        e, o, tc = self.engine, self.engine.ops, self.engine.cfg.text
+        if getattr(self, "batched_attn", False):      # (getattr: the host tests build group objects with __new__, without the attribute)
+            lens, chunks, has_lin = self._attn_host_args
+            o.decb_attn(tab, self.attn_table, B, self.q, self.attn, li, tc.num_heads, scale, lens, chunks, has_lin, e.kd // tc.head_dim,
+                        tc.head_dim)
+            return
+        for j, (lane, c) in enumerate(act):
+            o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
+                          lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+
     # ------------------------------------------------------------------ one batched decode step
     def _head(self, tab, B, sampled: bool):
         """The head and the token feedback.  `sampled`: some lane of the batch draws its token -- the head adds the Gumbel noise where a
@@ -306,7 +353,7 @@ class StreamGroup:
         o.decb_sample_finish(tab, self.samples, B, self.logits, self.suppress, self.ws, tc.vocab_size, 1)
 
     def _step_launch(self, act, sampled: bool = False):
-        """One token for every live lane of the batch: per layer [norm+QKV+append]xB-in-one, B x [attn split, attn combine],
+        """One token for every live lane of the batch: per layer [norm+QKV+append]xB-in-one, B x [attn split, attn combine] (`_attn`),
         [o+res]xB-in-one, [norm+gate/up+SwiGLU]xB-in-one, [down+res]xB-in-one; then the head and the token feedback."""
         e, o, w, tc = self.engine, self.engine.ops, self.engine.w, self.engine.cfg.text
         B, qd, kd, nl = len(act), e.qd, e.kd, len(self.engine.w.layers)
@@ -326,9 +373,7 @@ class StreamGroup:
             return
         for li, lw in enumerate(w.layers):
             o.decb_qkv(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
-            for j, (lane, c) in enumerate(act):          # the single-stream attention, once per lane, same stream (no forked branches)
-                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
-                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            self._attn(act, tab, B, li, scale)
             o.decb_gemv(tab, B, self.attn, lw["o_w"], self.x, self.x)
             o.decb_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
             o.decb_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
@@ -341,9 +386,7 @@ class StreamGroup:
         o.decw_embed(tab, B, w.embed, self.x)
         for li, lw in enumerate(w.layers):
             o.decw_qkv(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
-            for j, (lane, c) in enumerate(act):
-                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
-                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            self._attn(act, tab, B, li, scale)
             o.decw_gemv(tab, B, self.attn, lw["o_w"], self.x, self.x)
             o.decw_gate_up(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w"], self.h)
             o.decw_gemv(tab, B, self.h, lw["down_w"], self.x, self.x)
@@ -357,9 +400,7 @@ class StreamGroup:
         qd, kd, nl = e.qd, e.kd, len(w.layers)
         for li, lw in enumerate(w.layers):
             o.decb_qkv_fp8(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w8"], lw["qkv_w_s"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
-            for j, (lane, c) in enumerate(act):
-                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
-                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            self._attn(act, tab, B, li, scale)
             o.decb_gemv_fp8(tab, B, self.attn, lw["o_w8"], lw["o_w_s"], self.x, self.x)
             o.decb_gate_up_fp8(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w8"], lw["gu_w_s"], self.h)
             o.decb_gemv_fp8(tab, B, self.h, lw["down_w8"], lw["down_w_s"], self.x, self.x)
@@ -371,9 +412,7 @@ class StreamGroup:
         qd, kd, nl = e.qd, e.kd, len(w.layers)
         for li, lw in enumerate(w.layers):
             o.decb_qkv_fp4(tab, B, self.x, lw["ln1"], tc.rms_eps, lw["qkv_w4"], lw["qkv_w_s4"], lw["qkv_b"], self.q, li, qd, kd, tc.head_dim, nl)
-            for j, (lane, c) in enumerate(act):
-                o.decode_attn(self.q[j], c.pool, li, c.slot_of_dev, lane.rope_cs, self.attn[j], lane.d_ws, tc.num_heads, lane._attn_len,
-                              lane.decode_chunk, scale, length=1, len_dev=lane.state[0:1], lin=c.lin_args() if hasattr(c, "lin_args") else None)
+            self._attn(act, tab, B, li, scale)
             o.decb_gemv_fp4(tab, B, self.attn, lw["o_w4"], lw["o_w_s4"], self.x, self.x)
             o.decb_gate_up_fp4(tab, B, self.x, lw["ln2"], tc.rms_eps, lw["gu_w4"], lw["gu_w_s4"], self.h)
             o.decb_gemv_fp4(tab, B, self.h, lw["down_w4"], lw["down_w_s4"], self.x, self.x)
@@ -425,11 +464,17 @@ class StreamGroup:
             ctxs.append(ctx)
         B = len(act)
         dev_is_gpu = self.engine.device.type == "cuda"
+        batched_attn = getattr(self, "batched_attn", False)      # (as in `_attn`: group objects built without __init__)
         if B:
             for j, ((lane, c), ctx) in enumerate(zip(act, ctxs)):
                 self._write_row(j, self._record(lane, c, ctx.max_new_tokens), j)
                 if self.sampling:
                     self._write_sample_row(j, self._sample_record(lane))
+                if batched_attn:
+                    self._write_attn_row(j, self._attn_record(lane, c))
+            if batched_attn:
+                self._attn_host_args = ([lane._attn_len for lane, _ in act], [lane.decode_chunk for lane, _ in act],
+                                        [hasattr(c, "lin_args") and c.lin_args() is not None for _, c in act])
             sampled = self.sampling and any(lane._sampling is not None for lane, _ in act)
             n_steps = max(ctx.max_new_tokens for ctx in ctxs) - 1
             done = [False] * B                   # host view: an EOS was seen among the lane's tokens

@@ -39,6 +39,15 @@ profiles/stream_group_wide_<model>.json.  The decw_* kernel averages PER LANE CO
 (with --fold): the kernel names do not carry the lane count, so every step's kernels are filed under the lane count its embedding
 gather's grid shows.
 
+`--batched-attn` (with or without --wide): every group pass runs twice on the same model, in the same process and run -- the group as it
+is (the decode attention once per lane: `2 B n_layers` launches per step) and `StreamGroup(batched_attn=True)` (svlm_decb_attn: one
+launch pair per layer) -- `--attn-repeats` times each, alternating; per lane count the record holds the decode step (us, median and
+spread of the replay rounds) and the chunk round (ms, median and spread of the repeats) of both, their ratio, and whether the batched
+step is below the looped one by more than the two spreads together.  Writes profiles/stream_group_attn_<model>.json.  Per-launch averages
+of the batched pair against the single-lane pair come from a trace run of its own (no counters in it):
+`rocprofv3 --kernel-trace -- python tools/stream_group_bench.py --wide --batched-attn --kernels-only`, folded in with --kernel-trace
+--fold (the attention kernels of a step are filed under its lane count like the decb_* / decw_* kernels).
+
 Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- python tools/stream_group_bench.py --kernels-only`
 (a run of its own, no counters) and pass the stats CSV with --kernel-stats to have the decb_* / single-row averages folded in.
 
@@ -50,6 +59,7 @@ Kernel averages: run this script under `rocprofv3 --kernel-trace --stats -- pyth
     python tools/stream_group_bench.py --prefill-fp4 [--model 7b --fps 2 --window 4096]  (writes profiles/stream_group_prefill_fp4_<model>.json)
     python tools/stream_group_bench.py --sample 0.9 --sample 0.9,50,1.0               (writes profiles/stream_group_sampling_2b.json)
     python tools/stream_group_bench.py --wide                                         (writes profiles/stream_group_wide_2b.json)
+    python tools/stream_group_bench.py --wide --batched-attn                          (writes profiles/stream_group_attn_2b.json)
 """
 import argparse
 import csv
@@ -132,7 +142,7 @@ def kernel_trace_by_lanes(path, cfg):
         name = r[name_c]
         if "decb_embed_kernel" in name:
             lanes = int(r[gy_c]) // max(1, int(r[wy_c]) if wy_c else 1)
-        if lanes is None or not ("decb_" in name or "decw_" in name):
+        if lanes is None or not ("decb_" in name or "decw_" in name or "decode_attn" in name):
             continue
         a = acc.setdefault(name[:120], {}).setdefault(lanes, [0, 0])
         a[0] += 1
@@ -169,6 +179,9 @@ def main():
     ap.add_argument("--wide", action="store_true", help="also run StreamGroup(wide=True) at every lane count of --wide-lanes, read against the "
                                                         "existing groups of the same run")
     ap.add_argument("--wide-lanes", default="1,2,4,8,12,16", help="lane counts of the --wide passes")
+    ap.add_argument("--batched-attn", action="store_true", help="run every group (and --wide group) with and without batched_attn=True, alternating, "
+                                                                "and record both")
+    ap.add_argument("--attn-repeats", type=int, default=3, help="--batched-attn: timed passes per group and variant")
     ap.add_argument("--kernel-trace", default=None, help="rocprofv3 kernel_trace CSV of a --kernels-only run: lane-batched kernel averages per lane count")
     ap.add_argument("--kernels-only", action="store_true", help="one short pass per B and nothing else (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--kernel-stats", default=None, help="rocprofv3 kernel_stats CSV of a --kernels-only run")
@@ -201,8 +214,10 @@ def main():
     wide_lanes = [int(v) for v in args.wide_lanes.split(",")] if args.wide else []
     if args.wide and (args.llm_fp8 or args.llm_fp4 or settings):
         ap.error("--wide is bf16 weights and greedy decoding: not with --llm-fp8 / --llm-fp4 / --sample")
-    if args.wide and not args.kernels_only and not args.fold and args.out is None:
-        args.out = os.path.join(root, "profiles", f"stream_group_wide_{args.model}.json")
+    if (args.wide or args.batched_attn) and not args.kernels_only and not args.fold and args.out is None:
+        args.out = os.path.join(root, "profiles", f"stream_group_{'attn' if args.batched_attn else 'wide'}_{args.model}.json")
+    if args.batched_attn and (args.llm_fp8 or args.llm_fp4 or settings):
+        ap.error("--batched-attn measures the bf16 greedy groups (narrow and --wide); the flag itself combines with every engine")
     cfg = {"2b": C.qwen2_vl_2b, "7b": C.qwen2_vl_7b, "tiny": C.tiny}[args.model]()
     if args.fold:
         if not args.kernel_stats and not args.kernel_trace:
@@ -309,7 +324,60 @@ def main():
             del group
         return groups
 
-    groups = out["group"] = group_passes(model)
+    def attn_passes(m, wide=False):
+        """Every lane count with and without batched_attn=True: `--attn-repeats` timed passes each, alternating (a drift of the machine hits
+        both alike), and the decode step of each from the captured step graph of its last batch.  -> ({B: looped record}, {B: batched record +
+        comparison})"""
+        reps = 1 if args.kernels_only else max(1, args.attn_repeats)
+        looped, cmp_ = {}, {}
+        for B in (wide_lanes if wide else range(1, args.max_lanes + 1)):
+            pair = {}
+            for name, kw in (("looped", {}), ("batched", dict(batched_attn=True))):
+                pair[name] = [StreamGroup(m._svlm_engine, B, **kw, **(dict(wide=True) if wide else {})), []]
+            # A variant's step graph is replayed RIGHT AFTER that variant's own last pass: lane 0 of both groups is the model's engine, which
+            # keeps only its last cache alive (`_last_cache`), so once the other group has run a pass the pools, slot tables and planes this
+            # graph's launches address are gone.
+            steps_ = {}
+            for r in range(reps):
+                for name, (group, passes) in pair.items():
+                    passes.append(timed(lambda kws, g=group: S.streaming_inference_group(m, proc, kws, group=g), B, False))
+                    if r == reps - 1:
+                        ms_chunk = replay_decode(next(reversed(group._graphs.values()))[0], group.lanes, args.new_tokens - 1)
+                        steps_[name] = (ms_chunk, list(replay_decode.rounds_ms))
+            recs = {}
+            for name, (group, passes) in pair.items():
+                ms = [q["ms_per_chunk"] for q in passes]
+                rec = dict(passes[len(passes) // 2], passes_ms_per_chunk=ms, ms_per_chunk_median=statistics.median(ms), ms_per_chunk_spread=max(ms) - min(ms))
+                rec["decode_ms_per_chunk"], rounds_ms = steps_[name]
+                rec["decode_us_per_step"] = 1e3 * rec["decode_ms_per_chunk"] / (args.new_tokens - 1)
+                rec["decode_us_per_step_median"] = 1e3 * statistics.median(rounds_ms) / (args.new_tokens - 1)
+                rec["decode_us_per_step_spread"] = 1e3 * (max(rounds_ms) - min(rounds_ms)) / (args.new_tokens - 1)
+                recs[name] = rec
+            lo, ba = recs["looped"], recs["batched"]
+            step_spread = lo["decode_us_per_step_spread"] + ba["decode_us_per_step_spread"]
+            round_spread = lo["ms_per_chunk_spread"] + ba["ms_per_chunk_spread"]
+            print(f"[batched-attn] {'wide ' if wide else ''}{B} lanes: step {lo['decode_us_per_step_median']:.0f} -> {ba['decode_us_per_step_median']:.0f} us "
+                  f"(spreads {step_spread:.0f}), round {lo['ms_per_chunk_median']:.2f} -> {ba['ms_per_chunk_median']:.2f} ms", file=sys.stderr, flush=True)
+            looped[str(B)] = lo
+            cmp_[str(B)] = dict(batched=ba,                 # (the looped record is the plain group's: `group` / `group_wide` of the file)
+                                decode_step_batched_vs_looped=ba["decode_us_per_step_median"] / lo["decode_us_per_step_median"],
+                                decode_step_us_saved=lo["decode_us_per_step_median"] - ba["decode_us_per_step_median"],
+                                decode_step_spread_of_both_us=step_spread,
+                                decode_step_below_by_more_than_spread=lo["decode_us_per_step_median"] - ba["decode_us_per_step_median"] > step_spread,
+                                chunk_round_batched_vs_looped=ba["ms_per_chunk_median"] / lo["ms_per_chunk_median"],
+                                chunk_round_ms_saved=lo["ms_per_chunk_median"] - ba["ms_per_chunk_median"],
+                                chunk_round_spread_of_both_ms=round_spread,
+                                chunk_round_below_by_more_than_spread=lo["ms_per_chunk_median"] - ba["ms_per_chunk_median"] > round_spread)
+            del pair
+        return looped, cmp_
+
+    if args.batched_attn:
+        # (the looped side IS the plain group: it is measured once, here)
+        groups, narrow_cmp = attn_passes(model)
+        out["group"] = groups
+        out["batched_attn"] = dict(repeats=args.attn_repeats, group=narrow_cmp)
+    else:
+        groups = out["group"] = group_passes(model)
     out["llm_fp8"] = bool(args.llm_fp8)
     out["prefill_fp8"] = bool(args.prefill_fp8)
     out["llm_fp4"] = bool(args.llm_fp4)
@@ -369,7 +437,11 @@ def main():
             out["best"].update(solo_fp4_frames_per_sec=ref, solo_fp4_frames_per_sec_spread=max(fps_solo) - min(fps_solo))
     if args.wide:
         # the wide groups of the same model, same process, same run: read against the existing groups above, never against another day's
-        gw = out["group_wide"] = group_passes(model, wide=True)
+        if args.batched_attn:
+            gw, out["batched_attn"]["group_wide"] = attn_passes(model, wide=True)
+            out["group_wide"] = gw
+        else:
+            gw = out["group_wide"] = group_passes(model, wide=True)
         for B, rec in gw.items():
             if "solo" in out:
                 rec["aggregate_frames_per_sec_vs_solo"] = rec["frames_per_sec"] / ref
