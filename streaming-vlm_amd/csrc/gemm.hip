@@ -16,6 +16,8 @@
 // tile grid cannot cover the 256 CUs the K range is split over grid.z, fp32 partial slabs go to a
 // caller-provided workspace and a second kernel sums them and applies the epilogue.
 #include "common.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 #define GEMM_BN 128
@@ -41,26 +43,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16_t* __restrict
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // ---- workgroup -> (tile, K-split).  Workgroups are dealt round-robin over the 8 XCDs (private 4 MiB L2 each), so
-  // bid % 8 names the XCD group.  Speed only, never correctness:
-  //   split-K : the split index varies fastest -> an XCD only ever touches ONE K-slice of A and W (fits its L2)
-  //   no split: each XCD owns a contiguous range of n-tiles and walks m fastest -> a W tile is fetched once and
-  //             reused by all m-tiles from L2, the (smaller) A panel is what gets re-streamed
-  const int bid = blockIdx.x;
   int tm, tn, split;
-  if (splits > 1) {
-    split = bid % splits;
-    const int t = bid / splits;
-    tn = t % gn;
-    tm = t / gn;
-  } else {
-    split = 0;
-    const int npx = (gn + 7) / 8;
-    const int local = bid / 8;
-    tn = (bid % 8) * npx + local / gm;
-    tm = local % gm;
-    if (tn >= gn) return;          // whole workgroup: the grid is padded to 8 * npx * gm
-  }
+  if (!gemm_tile_of(blockIdx.x, gm, gn, splits, tm, tn, split)) return;
   const int m0 = tm * BM, n0 = tn * GEMM_BN;
   const int lrow = tid >> 3, lchunk = tid & 7;  // loader: 8 threads cover one 128-B row segment
   const int k_begin = split * k_per_split;
@@ -149,36 +133,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16_t* __restrict
     lds_barrier();
   }
 
-  // epilogue: lane holds m = fr (column of D), n = 4*fq + r (rows of D)
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wm * 16 * TM + i * 16 + fr;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + fq * 4;
-      if (n >= N) continue;
-      if (partial) {  // split-K: raw fp32 slab, the epilogue runs in the reduce kernel
-        *reinterpret_cast<f32x4_t*>(partial + ((size_t)split * M + m) * N + n) = acc[i][j];
-        continue;
-      }
-      float y[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (bias) {
-        u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-        y[0] += lo_bf(bv[0]); y[1] += hi_bf(bv[0]); y[2] += lo_bf(bv[1]); y[3] += hi_bf(bv[1]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) y[r] = apply_act(rbf(y[r]), act);
-      if (residual) {
-        u32x2_t rv = *reinterpret_cast<const u32x2_t*>(residual + (size_t)m * ldr + n);
-        y[0] = y[0] + lo_bf(rv[0]); y[1] = y[1] + hi_bf(rv[0]); y[2] = y[2] + lo_bf(rv[1]); y[3] = y[3] + hi_bf(rv[1]);
-      }
-      u32x2_t o;
-      o[0] = pack2(y[0], y[1]);
-      o[1] = pack2(y[2], y[3]);
-      *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-    }
-  }
+  gemm_tile_epilogue<TM>(acc, m0, n0, wm, wn, fr, fq, split, M, N, bias, residual, ldr, C, ldc, partial, act);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -220,21 +175,8 @@ __global__ __launch_bounds__(128 * WM) void gemm_glds_kernel(const bf16_t* __res
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = blockIdx.x;
   int tm, tn, split;
-  if (splits > 1) {
-    split = bid % splits;
-    const int t = bid / splits;
-    tn = t % gn;
-    tm = t / gn;
-  } else {
-    split = 0;
-    const int npx = (gn + 7) / 8;
-    const int local = bid / 8;
-    tn = (bid % 8) * npx + local / gm;
-    tm = local % gm;
-    if (tn >= gn) return;
-  }
+  if (!gemm_tile_of(blockIdx.x, gm, gn, splits, tm, tn, split)) return;
   const bool swiglu = act == SVLM_ACT_SWIGLU;     // 64 output columns per tile: gate | up halves of the 128 tile columns
   const int m0 = tm * BM, n0 = tn * (swiglu ? GEMM_BN / 2 : GEMM_BN);
   const int k_begin = split * k_per_split;
@@ -253,9 +195,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_glds_kernel(const bf16_t* __res
 #pragma unroll
   for (int i = 0; i < W_INST; ++i) {
     const int row = (wave * W_INST + i) * 8 + rsub;
-    // SwiGLU pairing: tile rows 0..63 are gate rows n0.., tile rows 64..127 the matching up rows N + n0.. (N = output columns)
-    const int wrow = swiglu ? (row < 64 ? min(n0 + row, N - 1) : N + min(n0 + row - 64, N - 1)) : min(n0 + row, N - 1);
-    w_src[i] = W + (size_t)wrow * ldw + k_begin + ((ppos ^ (row & 7)) * 8);
+    w_src[i] = W + (size_t)w_row(row, n0, N, swiglu) * ldw + k_begin + ((ppos ^ (row & 7)) * 8);
   }
   auto issue = [&](int kt, int stage) {
     unsigned char* sa = smem + stage * STAGE_B;
@@ -325,82 +265,10 @@ __global__ __launch_bounds__(128 * WM) void gemm_glds_kernel(const bf16_t* __res
 #endif
 
   if (swiglu) {
-    // the up half (waves wn = 1) hands its bf16-rounded values to the gate half through the staging LDS, which is free now
-    float* U = reinterpret_cast<float*>(smem);                       // [BM][64]
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (wn == 1) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f32x4_t u;
-          const int nb = min(n0 + j * 16 + fq * 4, N - 4);
-          float ub[4] = {0.f, 0.f, 0.f, 0.f};
-          if (bias) {                                        // up bias = second half of the [gate; up] bias vector
-            const u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + N + nb);
-            ub[0] = lo_bf(bv[0]); ub[1] = hi_bf(bv[0]); ub[2] = lo_bf(bv[1]); ub[3] = hi_bf(bv[1]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) u[r] = rbf(acc[i][j][r] + ub[r]);
-          *reinterpret_cast<f32x4_t*>(U + (wm * 16 * TM + i * 16 + fr) * 64 + j * 16 + fq * 4) = u;
-        }
-    }
-    __syncthreads();
-    if (wn == 0) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm * 16 * TM + i * 16 + fr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + j * 16 + fq * 4;
-          if (m >= M || n >= N) continue;
-          const f32x4_t u = *reinterpret_cast<const f32x4_t*>(U + (wm * 16 * TM + i * 16 + fr) * 64 + j * 16 + fq * 4);
-          float h[4], gb[4] = {0.f, 0.f, 0.f, 0.f};
-          if (bias) {
-            const u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-            gb[0] = lo_bf(bv[0]); gb[1] = hi_bf(bv[0]); gb[2] = lo_bf(bv[1]); gb[3] = hi_bf(bv[1]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h[r] = apply_act(rbf(acc[i][j][r] + gb[r]), SVLM_ACT_SILU) * u[r];
-          u32x2_t o;
-          o[0] = pack2(h[0], h[1]);
-          o[1] = pack2(h[2], h[3]);
-          *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-        }
-      }
-    }
+    gemm_tile_epilogue_swiglu<TM>(acc, smem, m0, n0, wm, wn, fr, fq, M, N, bias, C, ldc);
     return;
   }
-  // epilogue: lane holds m = fr (column of D), n = 4*fq + r (rows of D)
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wm * 16 * TM + i * 16 + fr;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + fq * 4;
-      if (n >= N) continue;
-      if (partial) {
-        *reinterpret_cast<f32x4_t*>(partial + ((size_t)split * M + m) * N + n) = acc[i][j];
-        continue;
-      }
-      float y[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (bias) {
-        u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-        y[0] += lo_bf(bv[0]); y[1] += hi_bf(bv[0]); y[2] += lo_bf(bv[1]); y[3] += hi_bf(bv[1]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) y[r] = apply_act(rbf(y[r]), act);
-      if (residual) {
-        u32x2_t rv = *reinterpret_cast<const u32x2_t*>(residual + (size_t)m * ldr + n);
-        y[0] = y[0] + lo_bf(rv[0]); y[1] = y[1] + hi_bf(rv[0]); y[2] = y[2] + lo_bf(rv[1]); y[3] = y[3] + hi_bf(rv[1]);
-      }
-      u32x2_t o;
-      o[0] = pack2(y[0], y[1]);
-      o[1] = pack2(y[2], y[3]);
-      *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-    }
-  }
+  gemm_tile_epilogue<TM>(acc, m0, n0, wm, wn, fr, fq, split, M, N, bias, residual, ldr, C, ldc, partial, act);
 }
 
 // C = epi(sum_z partial[z]) -- one thread per 4 consecutive n
@@ -596,9 +464,6 @@ extern "C" int svlm_diag_last_gemm_plan(int* out, int n) {
   return i;
 }
 #endif
-int svlm_gemm_reduce_launch(const float* partial, int splits, const void* bias, const void* residual, int ldr, void* C, int ldc, int M, int N,
-                            int act, const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn, void* stream, void* XN8 = nullptr,
-                            int ldxn8 = 0, float* xn_scale = nullptr);
 
 extern "C" int svlm_gemm_bf16(const void* A, int lda, const void* W, int ldw, const void* bias, const void* residual, int ldr,
                               void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes, void* stream) {
@@ -628,27 +493,9 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
   if (M == 0) return SVLM_OK;
   hipStream_t st = (hipStream_t)stream;
   const int gn = swiglu ? (N + GEMM_BN / 2 - 1) / (GEMM_BN / 2) : (N + GEMM_BN - 1) / GEMM_BN;      // SwiGLU: 64 output columns per tile
-  // ---- tile height and K-split from a small cost model.  The path's GEMMs are one or two "rounds" of resident
-  // workgroups, so quantisation decides: cost = rounds x K-steps per workgroup x step cost (+ slab traffic).
-  // Resident workgroups per CU: LDS 2 x (BM+128) x 128 B -> 48 KB (BM=64): 3, 64 KB (BM=128): 2.
-  int best_bm = 64, best_splits = 1;
-  double best_cost = 1e30;
-  for (int bm_c = 64; bm_c <= 128; bm_c += 64) {
-    if (bm_c == 128 && M <= 64) continue;
-    const long long tiles_c = (long long)((M + bm_c - 1) / bm_c) * gn;
-    const long long cap = 256LL * (bm_c == 64 ? 3 : 2);
-    const int max_s = ws != nullptr ? (K >= 1024 ? (K / 512 < 16 ? K / 512 : 16) : 1) : 1;
-    for (int sp = 1; sp <= max_s; ++sp) {
-      if (sp > 1 && (long long)sp * M * N * 4 > ws_bytes) break;
-      const long long wgs = tiles_c * sp;
-      const double rounds = (double)((wgs + cap - 1) / cap);
-      const double ksteps = (double)((K + sp - 1) / sp + GEMM_BK - 1) / GEMM_BK + 3.0;           // + prologue/epilogue
-      const double step_us = bm_c == 64 ? 0.9 : 1.5;                                              // measured per K-step
-      const double slab_us = sp > 1 ? 2.0 * sp * M * N * 4.0 / 3e12 * 1e6 + 5.0 : 0.0;            // slab write+read + reduce launch
-      const double cost = rounds * ksteps * step_us + slab_us;
-      if (cost < best_cost) { best_cost = cost; best_bm = bm_c; best_splits = sp; }
-    }
-  }
+  // ---- tile height and K-split from the cost model (gemm_plan.h)
+  int best_bm, best_splits;
+  gemm_cost_plan(M, N, K, gn, ws, ws_bytes, &best_bm, &best_splits);
   // ---- tuned plans: shapes of the supported models measured on MI355X (tools/gemm_tune_table.py, cold weights).  The cost
   // model above mis-ranks some of them (it knows nothing of co-resident workgroups sharing a CU's LDS-DMA stream); an entry
   // applies to its exact (N, K) and row bucket ceil(M/64) +- 1.
@@ -694,11 +541,7 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
   // gate/up 820 -> 886 TFLOP/s; 7B qkv (576 tiles = 2.25 rounds) stays on the 128-row tiles
   // (the 256-row tile exists on the LDS-DMA kernel only: a K that is not a multiple of 64 keeps the cost model's register-staged plan)
   const bool dma = (K % GEMM_BK == 0) && svlm_env("SVLM_GEMM_NO_DMA") == nullptr;
-  if (dma && M >= 2048 && K >= 2048 && best_splits == 1 && svlm_env("SVLM_GEMM_NO_T128") == nullptr) {
-    const long long t256 = (long long)((M + 255) / 256) * gn;
-    const long long rounds = (t256 + 255) / 256;
-    best_bm = (t256 * 100 >= rounds * 256 * 85) ? 256 : 128;
-  }
+  if (dma && M >= 2048 && K >= 2048 && best_splits == 1 && svlm_env("SVLM_GEMM_NO_T128") == nullptr) best_bm = gemm_large_m_bm(M, gn);
   if (const char* force = svlm_env("SVLM_GEMM_BM")) {       // tuning aid
     const int fb = atoi(force);
     best_bm = (fb == 192 || fb == 320 || fb == 256) ? fb : (fb == 128 && M > 64 ? 128 : 64);
@@ -714,146 +557,64 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, const void*
   const bool small = best_bm == 64;
   const int bm = best_bm;
   const int gm = (M + bm - 1) / bm;
-  int splits = best_splits;
-  int kps = K;
-  if (splits > 1) {
-    kps = ((K + splits - 1) / splits + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
-    splits = (K + kps - 1) / kps;
-  }
+  int splits = best_splits, kps;
+  gemm_finish_split(K, GEMM_BK, &splits, &kps);
   float* partial = splits > 1 ? (float*)ws : nullptr;
-  const int nblocks = splits > 1 ? gn * gm * splits : 8 * ((gn + 7) / 8) * gm;
-  dim3 grid(nblocks, 1, 1);
-  // waves / stages / dma are filled in where the kernel is picked below; a call that fails before its launch leaves them 0
+  const int nblocks = gemm_grid_size(gm, gn, splits);
+  // waves / stages / dma are filled in where the kernel is picked below
   SVLM_DIAG(g_svlm_gemm_plan_note = SvlmGemmPlanNote{g_svlm_gemm_plan_note.seq + 1, 0, bm, 0, 0, 0, splits, kps, table_hit ? 1 : 0, 0});
-  // LDS: two stages of (BM + 128) rows x 144 B -- above the 64 KB default for TM = 4, so opt in once
-  constexpr int LDS2 = 2 * (64 + GEMM_BN) * GEMM_LD * 2, LDS4 = 2 * (128 + GEMM_BN) * GEMM_LD * 2;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-      svlm_set_error("svlm_gemm_bf16: cannot reserve %d B of LDS: %s", LDS4, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-      return SVLM_ELAUNCH;
-    }
-    attr_done = true;
-  }
   if (!dma && (bm == 192 || bm == 320 || bm == 256 || swiglu)) {
     svlm_set_error("svlm_gemm_bf16: tall tiles and SVLM_ACT_SWIGLU run on the LDS-DMA kernel only (K %% 64 == 0, SVLM_GEMM_NO_DMA unset)");
     return SVLM_EINVAL;
   }
+  // dynamic LDS (above the 64 KB default for the taller tiles: gemm_launch opts in).  Register-staged: two stages of (BM + 128) rows
+  // x 128 B; LDS-DMA: `ns` stages of (BM + 128) rows x 128 B
+#define GEMM_REG_LDS(bm) (2 * ((bm) + GEMM_BN) * GEMM_LD * 2)
+#define GEMM_DMA_LDS(ns, bm) ((ns) * ((bm) + GEMM_BN) * 128)
+#define GEMM_LAUNCH(threads, lds, ...)                                                                                                    \
+  gemm_launch<&__VA_ARGS__, threads, lds>("svlm_gemm_bf16", nblocks, st, A, lda, W, ldw, bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, \
+                                          gn, splits)
+  int rc;
   if (dma) {
     // ring depth: 3 stages (72 KB at BM = 64: two workgroups per CU; 96 KB at BM = 128); 4 measured slower, see the kernel
-    constexpr int NS2 = 3, NS4 = 3;
-    constexpr int DLDS2 = NS2 * (64 + GEMM_BN) * 128, DLDS4 = NS4 * (128 + GEMM_BN) * 128;
-    static bool dma_attr_done = false;
-    if (!dma_attr_done) {
-      hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<2, NS2>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS2);
-      hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<4, NS4>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS4);
-      if (e1 != hipSuccess || e2 != hipSuccess) {
-        svlm_set_error("svlm_gemm_bf16: cannot reserve %d B of LDS: %s", DLDS4, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        return SVLM_ELAUNCH;
-      }
-      dma_attr_done = true;
-    }
     const bool tall_unsplit_ns2 = M >= 2048 || plan_ns2 || svlm_env("SVLM_GEMM_T128NS2") != nullptr;
     const bool w8_128 = svlm_env("SVLM_GEMM_W8") != nullptr;              // tuning aid: force the 8-wave 128 x 128 tile
     if (bm == 128 && splits == 1 && !swiglu && (w8_128 || plan_w8)) {
-      constexpr int DL = 3 * (128 + GEMM_BN) * 128;
-      static bool w8s_done = false;
-      if (!w8s_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<2, 3, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, DL);
-        w8s_done = true;
-      }
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 8; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
-      gemm_glds_kernel<2, 3, 4><<<grid, 512, DL, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                                  (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = GEMM_LAUNCH(512, GEMM_DMA_LDS(3, 128), gemm_glds_kernel<2, 3, 4>);
     } else if (bm == 256) {
-      constexpr int NS8 = 3, DLDS8 = NS8 * (256 + GEMM_BN) * 128;
-      static bool w8_done = false;
-      if (!w8_done) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<4, NS8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS8);
-        if (e1 != hipSuccess) {
-          svlm_set_error("svlm_gemm_bf16: cannot reserve %d B of LDS: %s", DLDS8, hipGetErrorString(e1));
-          return SVLM_ELAUNCH;
-        }
-        w8_done = true;
-      }
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 8; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
-      gemm_glds_kernel<4, NS8, 4><<<grid, 512, DLDS8, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                                    (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = GEMM_LAUNCH(512, GEMM_DMA_LDS(3, 256), gemm_glds_kernel<4, 3, 4>);
     } else if (bm == 192 || bm == 320) {
       // tall tiles for skinny-M weight-streaming GEMMs (prefill: M ~ 290): 2 x 192 rows, or ALL rows in one 320-row tile so that
       // W is streamed exactly once; 320 rows leave LDS for a 2-stage ring only
-      constexpr int DLDS6 = 3 * (192 + GEMM_BN) * 128, DLDS10 = 2 * (320 + GEMM_BN) * 128;
-      static bool tall_attr_done = false;
-      if (!tall_attr_done) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<6, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS6);
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<10, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS10);
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-          svlm_set_error("svlm_gemm_bf16: cannot reserve %d B of LDS: %s", DLDS10, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-          return SVLM_ELAUNCH;
-        }
-        tall_attr_done = true;
-      }
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = bm == 192 ? 3 : 2; g_svlm_gemm_plan_note.dma = 1);
-      if (bm == 192)
-        gemm_glds_kernel<6, 3><<<grid, 256, DLDS6, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                                 (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-      else
-        gemm_glds_kernel<10, 2><<<grid, 256, DLDS10, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                                  (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = bm == 192 ? GEMM_LAUNCH(256, GEMM_DMA_LDS(3, 192), gemm_glds_kernel<6, 3>) : GEMM_LAUNCH(256, GEMM_DMA_LDS(2, 320), gemm_glds_kernel<10, 2>);
     } else if (small && splits == 1 && svlm_env("SVLM_GEMM_NS3") == nullptr) {
       // un-split 64-row tiles on a 2-stage ring: 48 KB of LDS, THREE workgroups per CU -- one tile in flight each, the others' MFMAs
       // cover its wait.  Measured against the 3-stage ring (72 KB, two per CU; tools/gemm_shapes.py shapes, MI355X): ViT fc1
       // 31.5 -> 26.6 us, prefill gate/up 36.5 -> 31.2 us, ViT qkv 21.4 -> 20.9 us; split-K shapes are unchanged and keep 3 stages.
-      constexpr int DLDS2S = 2 * (64 + GEMM_BN) * 128;
-      static bool ns2_done = false;
-      if (!ns2_done) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS2S);
-        if (e1 != hipSuccess) {
-          svlm_set_error("svlm_gemm_bf16: cannot reserve %d B of LDS: %s", DLDS2S, hipGetErrorString(e1));
-          return SVLM_ELAUNCH;
-        }
-        ns2_done = true;
-      }
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 1);
-      gemm_glds_kernel<2, 2><<<grid, 256, DLDS2S, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                               (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = GEMM_LAUNCH(256, GEMM_DMA_LDS(2, 64), gemm_glds_kernel<2, 2>);
     } else if (!small && splits == 1 && tall_unsplit_ns2) {
       // un-split 128-row tiles on a 2-stage ring: 64 KB of LDS, TWO workgroups per CU (large-M GEMMs: the dense prefill's 4096-row
       // passes, the ViT's 8-grid batches)
-      constexpr int DLDS4S = 2 * (128 + GEMM_BN) * 128;
-      static bool ns2t_done = false;
-      if (!ns2t_done) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, DLDS4S);
-        if (e1 != hipSuccess) {
-          svlm_set_error("svlm_gemm_bf16: cannot reserve %d B of LDS: %s", DLDS4S, hipGetErrorString(e1));
-          return SVLM_ELAUNCH;
-        }
-        ns2t_done = true;
-      }
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 1);
-      gemm_glds_kernel<4, 2><<<grid, 256, DLDS4S, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                               (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = GEMM_LAUNCH(256, GEMM_DMA_LDS(2, 128), gemm_glds_kernel<4, 2>);
     } else if (small) {
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
-      gemm_glds_kernel<2, NS2><<<grid, 256, DLDS2, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                               (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = GEMM_LAUNCH(256, GEMM_DMA_LDS(3, 64), gemm_glds_kernel<2, 3>);
     } else {
       SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 3; g_svlm_gemm_plan_note.dma = 1);
-      gemm_glds_kernel<4, NS4><<<grid, 256, DLDS4, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                               (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+      rc = GEMM_LAUNCH(256, GEMM_DMA_LDS(3, 128), gemm_glds_kernel<4, 3>);
     }
-  } else if (small) {
-    SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 0);
-    gemm_bf16_kernel<2><<<grid, 256, LDS2, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                             (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
   } else {
     SVLM_DIAG(g_svlm_gemm_plan_note.waves = 4; g_svlm_gemm_plan_note.stages = 2; g_svlm_gemm_plan_note.dma = 0);
-    gemm_bf16_kernel<4><<<grid, 256, LDS4, st>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                             (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+    rc = small ? GEMM_LAUNCH(256, GEMM_REG_LDS(64), gemm_bf16_kernel<2>) : GEMM_LAUNCH(256, GEMM_REG_LDS(128), gemm_bf16_kernel<4>);
   }
-  int rc = svlm_check_launch("svlm_gemm_bf16");
+#undef GEMM_LAUNCH
+#undef GEMM_DMA_LDS
+#undef GEMM_REG_LDS
   if (rc) return rc;
   return svlm_gemm_reduce_launch(partial, splits, bias, residual, ldr, C, ldc, M, N, act, norm_w, norm_b, eps, XN, ldxn, stream);
 }

@@ -1,7 +1,8 @@
 // FP8 (OCP e4m3, gfx950) MFMA GEMM for the ViT of BASELINE configs[4]:  C[M,N] = epi((A8 . W8^T) * sa[m] * sw[n])
 //   A8 (M,K) fp8 with one fp32 scale per ROW (dynamic, from svlm_quant_rows_fp8), W8 (N,K) fp8 with one fp32 scale per output
 //   channel (static, quantised once when the weights are loaded);
-//   epi(y): y = bf16(y + bias[n]); y = act(y); y = bf16(y + residual[m,n]) -- the epilogue of svlm_gemm_bf16.
+//   epi(y): y = bf16(y + bias[n]); y = act(y); y = bf16(y + residual[m,n]) -- gemm_tile.h:gemm_tile_epilogue; split rounding, grid and
+//   launch: gemm_plan.h.
 // The reference has no fp8 path (its ViT GEMMs are third-party bf16 cuBLAS calls: qwen2/vision_forward.py:14,33,43-49,57,80);
 // the arithmetic is pinned by the oracle's linear_fp8 (oracle/model.py), which quantises with the same recipe.
 //
@@ -10,6 +11,8 @@
 // bytes and feeds TWICE the MFMA work (4 x v_mfma_f32_16x16x32_fp8_fp8 k-steps per tile instead of 2 bf16 ones): the K loop of
 // these skinny GEMMs is bound by the L2 -> LDS stream (gemm.hip), and fp8 halves the bytes per FLOP.
 #include "common.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 #define F8_BN 128
@@ -34,21 +37,8 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(const unsigned char* __re
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = blockIdx.x;
   int tm, tn, split;
-  if (splits > 1) {
-    split = bid % splits;
-    const int t = bid / splits;
-    tn = t % gn;
-    tm = t / gn;
-  } else {
-    split = 0;
-    const int npx = (gn + 7) / 8;
-    const int local = bid / 8;
-    tn = (bid % 8) * npx + local / gm;
-    tm = local % gm;
-    if (tn >= gn) return;
-  }
+  if (!gemm_tile_of(blockIdx.x, gm, gn, splits, tm, tn, split)) return;
   const int m0 = tm * BM, n0 = tn * F8_BN;
   const int k_begin = split * k_per_split;
   const int k_end = min(K, k_begin + k_per_split);
@@ -146,40 +136,20 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(const unsigned char* __re
     if (kt + AHEAD < nk) issue(kt + AHEAD, (kt + AHEAD) % NS);
     compute(kt % NS);
   }
-  // epilogue: lane holds m = fr (column of D), n = 4*fq + r (rows of D); scales first, then the bf16 epilogue of svlm_gemm_bf16
+  // lane holds m = fr (column of D), n = 4*fq + r (rows of D): the scales first, in place (the split-K slabs hold SCALED partials),
+  // then the shared epilogue.  Branch-free: a fragment past M or N takes the scales of the last row / column group and is never
+  // stored (guarded scaling made every fragment a merge of two values and cost 2-6 % on the ViT shapes).
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wm * 16 * TM + i * 16 + fr;
-    if (m >= M) continue;
-    const float sa_m = a_scale[m];
+    const float sa_m = a_scale[min(m0 + wm * 16 * TM + i * 16 + fr, M - 1)];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + fq * 4;
-      if (n >= N) continue;
-      const f32x4_t sw4 = *reinterpret_cast<const f32x4_t*>(w_scale + n);
-      float y[4];
+      const f32x4_t sw4 = *reinterpret_cast<const f32x4_t*>(w_scale + min(n0 + wn * 64 + j * 16 + fq * 4, N - 4));      // N % 4 == 0
 #pragma unroll
-      for (int r = 0; r < 4; ++r) y[r] = acc[i][j][r] * (sa_m * sw4[r]);
-      if (partial) {
-        *reinterpret_cast<f32x4_t*>(partial + ((size_t)split * M + m) * N + n) = f32x4_t{y[0], y[1], y[2], y[3]};
-        continue;
-      }
-      if (bias) {
-        u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-        y[0] += lo_bf(bv[0]); y[1] += hi_bf(bv[0]); y[2] += lo_bf(bv[1]); y[3] += hi_bf(bv[1]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) y[r] = apply_act(rbf(y[r]), act);
-      if (residual) {
-        u32x2_t rv = *reinterpret_cast<const u32x2_t*>(residual + (size_t)m * ldr + n);
-        y[0] = y[0] + lo_bf(rv[0]); y[1] = y[1] + hi_bf(rv[0]); y[2] = y[2] + lo_bf(rv[1]); y[3] = y[3] + hi_bf(rv[1]);
-      }
-      u32x2_t o;
-      o[0] = pack2(y[0], y[1]);
-      o[1] = pack2(y[2], y[3]);
-      *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
+      for (int r = 0; r < 4; ++r) acc[i][j][r] = acc[i][j][r] * (sa_m * sw4[r]);
     }
   }
+  gemm_tile_epilogue<TM>(acc, m0, n0, wm, wn, fr, fq, split, M, N, bias, residual, ldr, C, ldc, partial, act);
 }
 
 // ---------------------------------------------------------------- row quantiser: bf16 (rows, cols) -> fp8 e4m3 + one fp32 scale per row
@@ -222,11 +192,6 @@ extern "C" int svlm_quant_rows_fp8(const void* x, int ldx, void* q, int ldq, flo
   quant_rows_fp8_kernel<<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>((const bf16_t*)x, ldx, (unsigned char*)q, ldq, scale, rows, cols);
   return svlm_check_launch("svlm_quant_rows_fp8");
 }
-
-// split-K reduce kernels of gemm.hip (the fp8 kernel writes SCALED fp32 partials, so the bf16 reduce epilogues apply as they are)
-int svlm_gemm_reduce_launch(const float* partial, int splits, const void* bias, const void* residual, int ldr, void* C, int ldc, int M, int N,
-                            int act, const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn, void* stream, void* XN8 = nullptr,
-                            int ldxn8 = 0, float* xn_scale = nullptr);
 
 static int gemm_fp8_impl(const void* A8, int lda, const float* a_scale, const void* W8, int ldw, const float* w_scale, const void* bias,
                          const void* residual, int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes,
@@ -279,33 +244,18 @@ static int gemm_fp8_impl(const void* A8, int lda, const float* a_scale, const vo
   if (const char* fs = svlm_env("SVLM_GEMM8_SPLITS")) { const int v = atoi(fs); if (v >= 1 && (v == 1 || (ws && (long long)v * M * N * 4 <= ws_bytes))) splits = v; }
   if (const char* fb = svlm_env("SVLM_GEMM8_BM")) { const int v = atoi(fb); if (v == 64 || v == 128) bm = v; }
   if (norm_w != nullptr && splits == 1 && ws != nullptr && K >= 1024 && (long long)2 * M * N * 4 <= ws_bytes && N <= 4096) splits = 2;   // the reduce carries the norm
-  int kps = K;
-  if (splits > 1) {
-    kps = ((K + splits - 1) / splits + F8_BK - 1) / F8_BK * F8_BK;
-    splits = (K + kps - 1) / kps;
-  }
+  int kps;
+  gemm_finish_split(K, F8_BK, &splits, &kps);
   const int gm = (M + bm - 1) / bm;
   float* partial = splits > 1 ? (float*)ws : nullptr;
-  const int nblocks = splits > 1 ? gn * gm * splits : 8 * ((gn + 7) / 8) * gm;
+  const int nblocks = gemm_grid_size(gm, gn, splits);
   SVLM_DIAG(g_svlm_gemm_plan_note = SvlmGemmPlanNote{g_svlm_gemm_plan_note.seq + 1, 1, bm, 4, 3, 1, splits, kps, 0, 0});
-  constexpr int L2 = 3 * (64 + F8_BN) * 128, L4 = 3 * (128 + F8_BN) * 128;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fp8_kernel<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, L2);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fp8_kernel<4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, L4);
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-      svlm_set_error("svlm_gemm_fp8: cannot reserve %d B of LDS: %s", L4, hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-      return SVLM_ELAUNCH;
-    }
-    attr_done = true;
-  }
-  if (bm == 64)
-    gemm_fp8_kernel<2, 3><<<nblocks, 256, L2, st>>>((const unsigned char*)A8, lda, a_scale, (const unsigned char*)W8, ldw, w_scale, (const bf16_t*)bias,
-                                                  (const bf16_t*)residual, ldr, (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-  else
-    gemm_fp8_kernel<4, 3><<<nblocks, 256, L4, st>>>((const unsigned char*)A8, lda, a_scale, (const unsigned char*)W8, ldw, w_scale, (const bf16_t*)bias,
-                                                  (const bf16_t*)residual, ldr, (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-  int rc = svlm_check_launch("svlm_gemm_fp8");
+  // LDS: three stages of (BM + 128) rows x 128 B
+#define F8_LAUNCH(TM)                                                                                                                      \
+  gemm_launch<&gemm_fp8_kernel<TM, 3>, 256, 3 * (32 * TM + F8_BN) * 128>("svlm_gemm_fp8", nblocks, st, A8, lda, a_scale, W8, ldw, w_scale, bias, \
+                                                                         residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits)
+  const int rc = bm == 64 ? F8_LAUNCH(2) : F8_LAUNCH(4);
+#undef F8_LAUNCH
   if (rc) return rc;
   if (splits > 1 || norm_w != nullptr)
     return svlm_gemm_reduce_launch(partial, splits, bias, residual, ldr, C, ldc, M, N, act, norm_w, norm_b, eps, XN, ldxn, stream, XN8, ldxn8, xn_scale);

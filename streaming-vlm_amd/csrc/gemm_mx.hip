@@ -1,8 +1,8 @@
 // MX prefill GEMM on the block-scaled MFMA:  C[M,N] = epi(A'[M,K] . W'[N,K]^T)
 //   A'[m,k] = e4m3(A8[m,k]) * 2^(a_scale[m,k/32] - 127)      MXFP8 activations (svlm_quant_mxfp8 below; weights.py:quantize_blocks_mxfp8)
 //   W'[n,k] = e2m1(W4[n,k]) * 2^(w_scale[n,k/32] - 127)      the MXFP4 language-model weights as EngineWeights holds them
-//   epi: the epilogue of svlm_gemm_bf16 (bias, activations 0..3, residual incl. in place, SVLM_ACT_SWIGLU on [gate rows; up rows],
-//   split-K through the caller's workspace, the norm of the output row inside the split-K reduce).
+//   epi: the tile epilogues of gemm_tile.h (bias, activations 0..3, residual incl. in place, SVLM_ACT_SWIGLU on [gate rows; up rows],
+//   split-K through the caller's workspace, the norm of the output row inside the split-K reduce); plan and launch: gemm_plan.h.
 // Both A' and W' are exactly representable in bf16 and every product is exact in fp32, so this is svlm_gemm_bf16 on (A', W') up to the
 // fp32 summation order.  The reference has bf16 activations; the rounding of the activations to e4m3 per block of 32 is this mode's
 // own numeric definition (opt-in: SvlmEngine(llm_fp4=True, prefill_mx=True)).
@@ -33,6 +33,8 @@
 // contiguous bytes per row in global memory (K % 128 == 0): one 4-B global_load_lds per row; a lane reads its byte with ds_read_u8.
 // One tile in flight = TM (A) + 2 (W) + 1 (scales) DMA instructions per wave, which is what the waits count.
 #include "common.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 #define MX_BN 128
@@ -63,21 +65,8 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const unsigned char* __res
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = blockIdx.x;
   int tm, tn, split;
-  if (splits > 1) {
-    split = bid % splits;
-    const int t = bid / splits;
-    tn = t % gn;
-    tm = t / gn;
-  } else {
-    split = 0;
-    const int npx = (gn + 7) / 8;
-    const int local = bid / 8;
-    tn = (bid % 8) * npx + local / gm;
-    tm = local % gm;
-    if (tn >= gn) return;          // whole workgroup: the grid is padded to 8 * npx * gm
-  }
+  if (!gemm_tile_of(blockIdx.x, gm, gn, splits, tm, tn, split)) return;
   const bool swiglu = act == SVLM_ACT_SWIGLU;     // 64 output columns per tile: gate | up halves of the 128 tile rows of W
   const int m0 = tm * BM, n0 = tn * (swiglu ? MX_BN / 2 : MX_BN);
   const int k_begin = split * k_per_split;
@@ -85,8 +74,6 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const unsigned char* __res
   const int nk = (k_end - k_begin) / MX_BK;       // K % 128 == 0 and k_per_split % 128 == 0
   const int nb = K >> 5;                          // scale bytes per row
 
-  // W row of tile row `row` (clamped: rows past N are computed on a valid row and never stored)
-  auto w_row = [&](int row) { return swiglu ? (row < 64 ? min(n0 + row, N - 1) : N + min(n0 + row - 64, N - 1)) : min(n0 + row, N - 1); };
 
   const unsigned char* a_src[A_INST];
   const unsigned char* w_src[W_INST];
@@ -98,11 +85,11 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const unsigned char* __res
 #pragma unroll
   for (int i = 0; i < W_INST; ++i) {              // W piece: row = piece * 16 + lane / 4, position lane % 4 holds chunk p ^ ((row >> 2) & 3)
     const int row = (wave * W_INST + i) * 16 + (lane >> 2);
-    w_src[i] = W4 + (size_t)w_row(row) * ldw + (k_begin >> 1) + (((lane & 3) ^ ((row >> 2) & 3)) * 16);
+    w_src[i] = W4 + (size_t)w_row(row, n0, N, swiglu) * ldw + (k_begin >> 1) + (((lane & 3) ^ ((row >> 2) & 3)) * 16);
   }
   // scales: waves 0, 1 bring the A rows 64 wave + lane (the second piece of a 64-row tile lands unused), waves 2, 3 the W rows
   const unsigned char* s_src = wave < 2 ? a_scale + (size_t)min(m0 + wave * 64 + lane, M - 1) * nb + (k_begin >> 5)
-                                        : w_scale + (size_t)w_row((wave - 2) * 64 + lane) * nb + (k_begin >> 5);
+                                        : w_scale + (size_t)w_row((wave - 2) * 64 + lane, n0, N, swiglu) * nb + (k_begin >> 5);
   auto issue = [&](int kt, int stage) {
     unsigned char* sa = smem + stage * STAGE_B;
     unsigned char* sw = sa + A_B;
@@ -162,82 +149,10 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(const unsigned char* __res
   }
 
   if (swiglu) {
-    // the up half (waves wn = 1) hands its bf16-rounded values to the gate half through the staging LDS, which is free now
-    float* U = reinterpret_cast<float*>(smem);                       // [BM][64]: BM x 256 B <= 3 stages
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (wn == 1) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f32x4_t u;
-          const int nbc = min(n0 + j * 16 + fq * 4, N - 4);
-          float ub[4] = {0.f, 0.f, 0.f, 0.f};
-          if (bias) {                                        // up bias = second half of the [gate; up] bias vector
-            const u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + N + nbc);
-            ub[0] = lo_bf(bv[0]); ub[1] = hi_bf(bv[0]); ub[2] = lo_bf(bv[1]); ub[3] = hi_bf(bv[1]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) u[r] = rbf(acc[i][j][r] + ub[r]);
-          *reinterpret_cast<f32x4_t*>(U + (wm * 16 * TM + i * 16 + fr) * 64 + j * 16 + fq * 4) = u;
-        }
-    }
-    __syncthreads();
-    if (wn == 0) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm * 16 * TM + i * 16 + fr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + j * 16 + fq * 4;
-          if (m >= M || n >= N) continue;
-          const f32x4_t u = *reinterpret_cast<const f32x4_t*>(U + (wm * 16 * TM + i * 16 + fr) * 64 + j * 16 + fq * 4);
-          float h[4], gb[4] = {0.f, 0.f, 0.f, 0.f};
-          if (bias) {
-            const u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-            gb[0] = lo_bf(bv[0]); gb[1] = hi_bf(bv[0]); gb[2] = lo_bf(bv[1]); gb[3] = hi_bf(bv[1]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h[r] = apply_act(rbf(acc[i][j][r] + gb[r]), SVLM_ACT_SILU) * u[r];
-          u32x2_t o;
-          o[0] = pack2(h[0], h[1]);
-          o[1] = pack2(h[2], h[3]);
-          *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-        }
-      }
-    }
+    gemm_tile_epilogue_swiglu<TM>(acc, smem, m0, n0, wm, wn, fr, fq, M, N, bias, C, ldc);
     return;
   }
-  // epilogue: lane holds m = fr (column of D), n = 4*fq + r (rows of D)
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wm * 16 * TM + i * 16 + fr;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + fq * 4;
-      if (n >= N) continue;
-      if (partial) {  // split-K: raw fp32 slab, the epilogue runs in the reduce kernel
-        *reinterpret_cast<f32x4_t*>(partial + ((size_t)split * M + m) * N + n) = acc[i][j];
-        continue;
-      }
-      float y[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (bias) {
-        u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-        y[0] += lo_bf(bv[0]); y[1] += hi_bf(bv[0]); y[2] += lo_bf(bv[1]); y[3] += hi_bf(bv[1]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) y[r] = apply_act(rbf(y[r]), act);
-      if (residual) {
-        u32x2_t rv = *reinterpret_cast<const u32x2_t*>(residual + (size_t)m * ldr + n);
-        y[0] = y[0] + lo_bf(rv[0]); y[1] = y[1] + hi_bf(rv[0]); y[2] = y[2] + lo_bf(rv[1]); y[3] = y[3] + hi_bf(rv[1]);
-      }
-      u32x2_t o;
-      o[0] = pack2(y[0], y[1]);
-      o[1] = pack2(y[2], y[3]);
-      *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-    }
-  }
+  gemm_tile_epilogue<TM>(acc, m0, n0, wm, wn, fr, fq, split, M, N, bias, residual, ldr, C, ldc, partial, act);
 }
 
 // ---------------------------------------------------------------- row quantiser: bf16 (rows, cols) -> MXFP8 (e4m3 codes + e8m0 per 32)
@@ -300,31 +215,6 @@ extern "C" int svlm_quant_mxfp8(const void* x, int ldx, void* q, int ldq, void* 
   return svlm_check_launch("svlm_quant_mxfp8");
 }
 
-// split-K reduce kernels of gemm.hip: the partial slabs are plain fp32, so the bf16 reduce epilogues (and the fused norm) apply as they are
-int svlm_gemm_reduce_launch(const float* partial, int splits, const void* bias, const void* residual, int ldr, void* C, int ldc, int M, int N,
-                            int act, const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn, void* stream, void* XN8 = nullptr,
-                            int ldxn8 = 0, float* xn_scale = nullptr);
-
-template <int TM>
-static int mx_launch(int nblocks, hipStream_t st, const void* A8, int lda, const void* a_scale, const void* W4, int ldw, const void* w_scale,
-                     const void* bias, const void* residual, int ldr, void* C, int ldc, float* partial, int M, int N, int K, int kps, int act,
-                     int gm, int gn, int splits) {
-  constexpr int LDS = 3 * (32 * TM * 128 + MX_BN * 64 + 1024);
-  static bool attr_done = false;          // one flag per instantiation
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mx_kernel<TM>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      svlm_set_error("svlm_gemm_mx_a8w4: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));
-      return SVLM_ELAUNCH;
-    }
-    attr_done = true;
-  }
-  gemm_mx_kernel<TM><<<dim3(nblocks, 1, 1), 256, LDS, st>>>((const unsigned char*)A8, lda, (const unsigned char*)a_scale, (const unsigned char*)W4,
-                                                            ldw, (const unsigned char*)w_scale, (const bf16_t*)bias, (const bf16_t*)residual, ldr,
-                                                            (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-  return svlm_check_launch("svlm_gemm_mx_a8w4");
-}
-
 static int gemm_mx_impl(const void* A8, int lda, const void* a_scale, const void* W4, int ldw, const void* w_scale, const void* bias,
                         const void* residual, int ldr, void* C, int ldc, int M, int N, int K, int act, void* ws, long long ws_bytes,
                         void* stream, const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn) {
@@ -366,20 +256,18 @@ static int gemm_mx_impl(const void* A8, int lda, const void* a_scale, const void
     if (v == 1 || (v > 1 && v <= K / MX_BK && can_split && (long long)v * M * N * 4 <= ws_bytes)) splits = v;
   }
   if (norm_w != nullptr && splits == 1 && can_split && K >= 2 * MX_BK && (long long)2 * M * N * 4 <= ws_bytes && N <= 4096) splits = 2;
-  int kps = K;
-  if (splits > 1) {
-    kps = ((K + splits - 1) / splits + MX_BK - 1) / MX_BK * MX_BK;
-    splits = (K + kps - 1) / kps;
-  }
+  int kps;
+  gemm_finish_split(K, MX_BK, &splits, &kps);
   const int gm = (M + bm - 1) / bm;
   float* partial = splits > 1 ? (float*)ws : nullptr;
-  const int nblocks = splits > 1 ? gn * gm * splits : 8 * ((gn + 7) / 8) * gm;
+  const int nblocks = gemm_grid_size(gm, gn, splits);
   SVLM_DIAG(g_svlm_gemm_plan_note = SvlmGemmPlanNote{g_svlm_gemm_plan_note.seq + 1, 4, bm, 4, 3, 1, splits, kps, 0, 0});
-  int rc;
-  if (bm == 128)
-    rc = mx_launch<4>(nblocks, st, A8, lda, a_scale, W4, ldw, w_scale, bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-  else
-    rc = mx_launch<2>(nblocks, st, A8, lda, a_scale, W4, ldw, w_scale, bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+  // LDS: three stages of A tile + W tile of codes + 1 KiB of scales
+#define MX_LAUNCH(TM)                                                                                                                        \
+  gemm_launch<&gemm_mx_kernel<TM>, 256, 3 * (32 * TM * 128 + MX_BN * 64 + 1024)>("svlm_gemm_mx_a8w4", nblocks, st, A8, lda, a_scale, W4, ldw, w_scale, \
+                                                                                 bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits)
+  const int rc = bm == 128 ? MX_LAUNCH(4) : MX_LAUNCH(2);
+#undef MX_LAUNCH
   if (rc) return rc;
   return svlm_gemm_reduce_launch(partial, splits, bias, residual, ldr, C, ldc, M, N, act, norm_w, norm_b, eps, XN, ldxn, stream);
 }

@@ -1,6 +1,6 @@
 // Weight-fp8, activation-bf16 MFMA GEMM:  C[M,N] = epi(A[M,K] . W'[N,K]^T),  W'[n,k] = e4m3(W8[n,k]) * w_scale[n]
-//   epi: the epilogue of svlm_gemm_bf16 (bias, activations 0..3, residual incl. in place, SVLM_ACT_SWIGLU on [gate rows; up rows],
-//   split-K through the caller's workspace, the norm of the output row inside the split-K reduce).
+//   epi: the tile epilogues of gemm_tile.h (bias, activations 0..3, residual incl. in place, SVLM_ACT_SWIGLU on [gate rows; up rows],
+//   split-K through the caller's workspace, the norm of the output row inside the split-K reduce); plan and launch: gemm_plan.h.
 // The prefill of an `llm_fp8` engine reads the e4m3 language-model weights with it instead of rebuilding every layer in bf16
 // (svlm_dequant_fp8_bf16 + svlm_gemm_bf16): the weight tile is staged as CODES, half the bytes and half the LDS-DMA pieces per
 // K-tile of gemm_glds_kernel (gemm.hip), and turned into bf16 when a wave reads its MFMA fragment -- once per W fragment, reused by
@@ -17,6 +17,8 @@
 // lane-linear (1 KiB piece = 16 rows x 64 B, lane i -> row i / 4, position i % 4), so the swizzle sits on the per-lane SOURCE
 // address and again on the fragment read.
 #include "common.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 #include <stdlib.h>
 
 #define WF_BN 128
@@ -60,30 +62,14 @@ __global__ __launch_bounds__(128 * WM) void gemm_wfp8_kernel(const bf16_t* __res
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // workgroup -> (tile, K-split): the order of gemm_glds_kernel (split index fastest; un-split: an XCD owns a range of n-tiles)
-  const int bid = blockIdx.x;
   int tm, tn, split;
-  if (splits > 1) {
-    split = bid % splits;
-    const int t = bid / splits;
-    tn = t % gn;
-    tm = t / gn;
-  } else {
-    split = 0;
-    const int npx = (gn + 7) / 8;
-    const int local = bid / 8;
-    tn = (bid % 8) * npx + local / gm;
-    tm = local % gm;
-    if (tn >= gn) return;          // whole workgroup: the grid is padded to 8 * npx * gm
-  }
+  if (!gemm_tile_of(blockIdx.x, gm, gn, splits, tm, tn, split)) return;
   const bool swiglu = act == SVLM_ACT_SWIGLU;     // 64 output columns per tile: gate | up halves of the 128 tile rows of W
   const int m0 = tm * BM, n0 = tn * (swiglu ? WF_BN / 2 : WF_BN);
   const int k_begin = split * k_per_split;
   const int k_end = min(K, k_begin + k_per_split);
   const int nk = (k_end - k_begin) / WF_BK;      // K % 64 == 0 and k_per_split % 64 == 0
 
-  // W row of tile row `row` (clamped: rows past N are computed on a valid row and never stored)
-  auto w_row = [&](int row) { return swiglu ? (row < 64 ? min(n0 + row, N - 1) : N + min(n0 + row - 64, N - 1)) : min(n0 + row, N - 1); };
 
   const bf16_t* a_src[A_INST];
   const unsigned char* w_src[W_INST];
@@ -95,14 +81,14 @@ __global__ __launch_bounds__(128 * WM) void gemm_wfp8_kernel(const bf16_t* __res
 #pragma unroll
   for (int i = 0; i < W_INST; ++i) {             // W piece: row = piece * 16 + lane / 4, position lane % 4 holds chunk p ^ ((row >> 2) & 3)
     const int row = (wave * W_INST + i) * 16 + (lane >> 2);
-    w_src[i] = W8 + (size_t)w_row(row) * ldw + k_begin + (((lane & 3) ^ ((row >> 2) & 3)) * 16);
+    w_src[i] = W8 + (size_t)w_row(row, n0, N, swiglu) * ldw + k_begin + (((lane & 3) ^ ((row >> 2) & 3)) * 16);
   }
   const int fr = lane & 15, fq = lane >> 4;
   // the scales of this lane's four W fragment rows; pinned here so that their loads are complete before the DMA ring starts and the
   // hand-counted vmcnt waits below see DMA pieces only
   float sc[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) sc[j] = w_scale[w_row(wn * 64 + j * 16 + fr)];
+  for (int j = 0; j < 4; ++j) sc[j] = w_scale[w_row(wn * 64 + j * 16 + fr, n0, N, swiglu)];
 #pragma unroll
   for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(sc[j]));
 
@@ -164,107 +150,10 @@ __global__ __launch_bounds__(128 * WM) void gemm_wfp8_kernel(const bf16_t* __res
   }
 
   if (swiglu) {
-    // the up half (waves wn = 1) hands its bf16-rounded values to the gate half through the staging LDS, which is free now
-    float* U = reinterpret_cast<float*>(smem);                       // [BM][64]
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (wn == 1) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f32x4_t u;
-          const int nb = min(n0 + j * 16 + fq * 4, N - 4);
-          float ub[4] = {0.f, 0.f, 0.f, 0.f};
-          if (bias) {                                        // up bias = second half of the [gate; up] bias vector
-            const u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + N + nb);
-            ub[0] = lo_bf(bv[0]); ub[1] = hi_bf(bv[0]); ub[2] = lo_bf(bv[1]); ub[3] = hi_bf(bv[1]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) u[r] = rbf(acc[i][j][r] + ub[r]);
-          *reinterpret_cast<f32x4_t*>(U + (wm * 16 * TM + i * 16 + fr) * 64 + j * 16 + fq * 4) = u;
-        }
-    }
-    __syncthreads();
-    if (wn == 0) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm * 16 * TM + i * 16 + fr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int n = n0 + j * 16 + fq * 4;
-          if (m >= M || n >= N) continue;
-          const f32x4_t u = *reinterpret_cast<const f32x4_t*>(U + (wm * 16 * TM + i * 16 + fr) * 64 + j * 16 + fq * 4);
-          float h[4], gb[4] = {0.f, 0.f, 0.f, 0.f};
-          if (bias) {
-            const u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-            gb[0] = lo_bf(bv[0]); gb[1] = hi_bf(bv[0]); gb[2] = lo_bf(bv[1]); gb[3] = hi_bf(bv[1]);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h[r] = apply_act(rbf(acc[i][j][r] + gb[r]), SVLM_ACT_SILU) * u[r];
-          u32x2_t o;
-          o[0] = pack2(h[0], h[1]);
-          o[1] = pack2(h[2], h[3]);
-          *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-        }
-      }
-    }
+    gemm_tile_epilogue_swiglu<TM>(acc, smem, m0, n0, wm, wn, fr, fq, M, N, bias, C, ldc);
     return;
   }
-  // epilogue: lane holds m = fr (column of D), n = 4*fq + r (rows of D)
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wm * 16 * TM + i * 16 + fr;
-    if (m >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + fq * 4;
-      if (n >= N) continue;
-      if (partial) {  // split-K: raw fp32 slab, the epilogue runs in the reduce kernel
-        *reinterpret_cast<f32x4_t*>(partial + ((size_t)split * M + m) * N + n) = acc[i][j];
-        continue;
-      }
-      float y[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (bias) {
-        u32x2_t bv = *reinterpret_cast<const u32x2_t*>(bias + n);
-        y[0] += lo_bf(bv[0]); y[1] += hi_bf(bv[0]); y[2] += lo_bf(bv[1]); y[3] += hi_bf(bv[1]);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) y[r] = apply_act(rbf(y[r]), act);
-      if (residual) {
-        u32x2_t rv = *reinterpret_cast<const u32x2_t*>(residual + (size_t)m * ldr + n);
-        y[0] = y[0] + lo_bf(rv[0]); y[1] = y[1] + hi_bf(rv[0]); y[2] = y[2] + lo_bf(rv[1]); y[3] = y[3] + hi_bf(rv[1]);
-      }
-      u32x2_t o;
-      o[0] = pack2(y[0], y[1]);
-      o[1] = pack2(y[2], y[3]);
-      *reinterpret_cast<u32x2_t*>(C + (size_t)m * ldc + n) = o;
-    }
-  }
-}
-
-// split-K reduce kernels of gemm.hip: the partial slabs are plain fp32, so the bf16 reduce epilogues (and the fused norm) apply as they are
-int svlm_gemm_reduce_launch(const float* partial, int splits, const void* bias, const void* residual, int ldr, void* C, int ldc, int M, int N,
-                            int act, const void* norm_w, const void* norm_b, float eps, void* XN, int ldxn, void* stream, void* XN8 = nullptr,
-                            int ldxn8 = 0, float* xn_scale = nullptr);
-
-template <int TM, int WM>
-static int wfp8_launch(int nblocks, hipStream_t st, const void* A, int lda, const void* W8, int ldw, const float* w_scale, const void* bias,
-                       const void* residual, int ldr, void* C, int ldc, float* partial, int M, int N, int K, int kps, int act, int gm, int gn,
-                       int splits) {
-  constexpr int LDS = 3 * (16 * TM * WM * 128 + WF_BN * 64);
-  static bool attr_done = false;          // one flag per instantiation
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wfp8_kernel<TM, WM>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      svlm_set_error("svlm_gemm_wfp8: cannot reserve %d B of LDS: %s", LDS, hipGetErrorString(e));
-      return SVLM_ELAUNCH;
-    }
-    attr_done = true;
-  }
-  gemm_wfp8_kernel<TM, WM><<<dim3(nblocks, 1, 1), 128 * WM, LDS, st>>>((const bf16_t*)A, lda, (const unsigned char*)W8, ldw, w_scale, (const bf16_t*)bias,
-                                                                         (const bf16_t*)residual, ldr, (bf16_t*)C, ldc, partial, M, N, K, kps, act, gm,
-                                                                         gn, splits);
-  return svlm_check_launch("svlm_gemm_wfp8");
+  gemm_tile_epilogue<TM>(acc, m0, n0, wm, wn, fr, fq, split, M, N, bias, residual, ldr, C, ldc, partial, act);
 }
 
 static int gemm_wfp8_impl(const void* A, int lda, const void* W8, int ldw, const float* w_scale, const void* bias, const void* residual, int ldr,
@@ -283,89 +172,18 @@ static int gemm_wfp8_impl(const void* A, int lda, const void* W8, int ldw, const
   if (M == 0) return SVLM_OK;
   hipStream_t st = (hipStream_t)stream;
   const int gn = swiglu ? (N + WF_BN / 2 - 1) / (WF_BN / 2) : (N + WF_BN - 1) / WF_BN;
-  // ---- tile height and K-split: the cost model of svlm_gemm_bf16 (rounds of resident workgroups x K-steps x step cost + slab
-  // traffic).  Resident workgroups per CU: LDS 3 x (BM x 128 + 8192) B -> 48 KB (BM = 64): 3, 72 KB (BM = 128): 2 -- the residency of
-  // the bf16 tiles, so a shape without a table entry gets the K per split its bf16 twin gets and reproduces it bit for bit.
-  int best_bm = 64, best_splits = 1;
-  double best_cost = 1e30;
-  for (int bm_c = 64; bm_c <= 128; bm_c += 64) {
-    if (bm_c == 128 && M <= 64) continue;
-    const long long tiles_c = (long long)((M + bm_c - 1) / bm_c) * gn;
-    const long long cap = 256LL * (bm_c == 64 ? 3 : 2);
-    const int max_s = ws != nullptr ? (K >= 1024 ? (K / 512 < 16 ? K / 512 : 16) : 1) : 1;
-    for (int sp = 1; sp <= max_s; ++sp) {
-      if (sp > 1 && (long long)sp * M * N * 4 > ws_bytes) break;
-      const long long wgs = tiles_c * sp;
-      const double rounds = (double)((wgs + cap - 1) / cap);
-      const double ksteps = (double)((K + sp - 1) / sp + WF_BK - 1) / WF_BK + 3.0;
-      const double step_us = bm_c == 64 ? 0.9 : 1.5;
-      const double slab_us = sp > 1 ? 2.0 * sp * M * N * 4.0 / 3e12 * 1e6 + 5.0 : 0.0;
-      const double cost = rounds * ksteps * step_us + slab_us;
-      if (cost < best_cost) { best_cost = cost; best_bm = bm_c; best_splits = sp; }
-    }
-  }
-  // ---- the language-model shapes the cost model mis-ranks: exact (N, K), row bucket ceil(M / 64) +- 1.  The split counts are those
-  // of the bf16 table (the prefill of a prefill_fp8 engine then equals the scratch-layer prefill bit for bit); this kernel has no
-  // tile taller than 128 rows below M = 2048, so the 7B down_proj keeps its 8 splits on 128-row tiles.
-  struct WfPlan { int mb, N, K, bm, splits; };
-  static const WfPlan kPlans[] = {
-      {5, 1536, 8960, 64, 4},      // Qwen2-VL-2B down_proj
-      {5, 4608, 3584, 64, 2},      // 7B qkv
-      {5, 3584, 3584, 64, 3},      // 7B o_proj
-      {5, 3584, 18944, 128, 8},    // 7B down_proj
-      {10, 3584, 18944, 128, 3},   // 7B down_proj at two temporal grids per chunk (M ~ 590)
-      {10, 18944, 3584, 128, 1},   // 7B gate/up (SwiGLU pairing) at M ~ 590
-      {5, 2560, 2048, 64, 3},      // Qwen2.5-VL-3B qkv
-      {5, 2048, 2048, 64, 3},      // 3B o_proj
-      {5, 2048, 11008, 64, 4},     // 3B down_proj
-  };
-  bool table_hit = false;
-  if (svlm_env("SVLM_GEMM_WFP8_NO_TABLE") == nullptr) {
-    const int mb = (M + 63) / 64;
-    for (const WfPlan& p : kPlans) {
-      if (p.N == N && p.K == K && mb >= p.mb - 1 && mb <= p.mb + 1 && (p.splits == 1 || (ws != nullptr && (long long)p.splits * M * N * 4 <= ws_bytes))) {
-        best_bm = p.bm;
-        best_splits = p.splits;
-        table_hit = true;
-        break;
-      }
-    }
-  }
-  // large-M, long-K GEMMs (4096-row passes of a dense prefill): un-split, 256 x 128 tiles on 8 waves where their grid fills whole
-  // rounds of the 256 CUs, else 128-row tiles -- the rule of svlm_gemm_bf16
-  if (M >= 2048 && K >= 2048 && best_splits == 1) {
-    const long long t256 = (long long)((M + 255) / 256) * gn;
-    const long long rounds = (t256 + 255) / 256;
-    best_bm = (t256 * 100 >= rounds * 256 * 85) ? 256 : 128;
-  }
-  if (const char* force = svlm_env("SVLM_GEMM_WFP8_BM")) {       // tuning aid
-    const int fb = atoi(force);
-    best_bm = fb == 256 ? 256 : (fb == 128 ? 128 : 64);
-    table_hit = false;
-    if (const char* fs = svlm_env("SVLM_GEMM_WFP8_SPLITS")) best_splits = atoi(fs) > 0 ? atoi(fs) : 1; else best_splits = 1;
-    if ((long long)best_splits * M * N * 4 > ws_bytes || ws == nullptr || K < 1024) best_splits = 1;
-  }
-  if (swiglu) best_splits = 1;        // one K pass: the pairing happens in the epilogue
-  const int bm = best_bm;
-  const int gm = (M + bm - 1) / bm;
-  int splits = best_splits;
-  int kps = K;
-  if (splits > 1) {
-    kps = ((K + splits - 1) / splits + WF_BK - 1) / WF_BK * WF_BK;
-    splits = (K + kps - 1) / kps;
-  }
-  float* partial = splits > 1 ? (float*)ws : nullptr;
-  const int nblocks = splits > 1 ? gn * gm * splits : 8 * ((gn + 7) / 8) * gm;
-  SVLM_DIAG(g_svlm_gemm_plan_note = SvlmGemmPlanNote{g_svlm_gemm_plan_note.seq + 1, 2, bm, bm == 256 ? 8 : 4, 3, 1, splits, kps, table_hit ? 1 : 0, 0});
-  int rc;
-  if (bm == 256)
-    rc = wfp8_launch<4, 4>(nblocks, st, A, lda, W8, ldw, w_scale, bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-  else if (bm == 128)
-    rc = wfp8_launch<4, 2>(nblocks, st, A, lda, W8, ldw, w_scale, bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
-  else
-    rc = wfp8_launch<2, 2>(nblocks, st, A, lda, W8, ldw, w_scale, bias, residual, ldr, C, ldc, partial, M, N, K, kps, act, gm, gn, splits);
+  // ---- tile height and K-split: the plan of svlm_gemm_bf16 on this kernel's tiles (gemm_plan.h:gemm_wcode_plan; a shape gets the K
+  // per split its bf16 twin gets and reproduces it bit for bit), which also writes the plan note
+  const GemmWPlan p = gemm_wcode_plan("SVLM_GEMM_WFP8", 2, M, N, K, gn, swiglu, ws, ws_bytes);
+  float* partial = p.splits > 1 ? (float*)ws : nullptr;
+  // LDS: three stages of A tile (BM rows x 128 B) + W tile of codes
+#define W_LAUNCH(TM, WM)                                                                                                                   \
+  gemm_launch<&gemm_wfp8_kernel<TM, WM>, 128 * WM, 3 * (16 * TM * WM * 128 + WF_BN * 64)>("svlm_gemm_wfp8", p.nblocks, st, A, lda, W8, ldw, w_scale, bias, residual, \
+                                                                                  ldr, C, ldc, partial, M, N, K, p.kps, act, p.gm, gn, p.splits)
+  const int rc = p.bm == 256 ? W_LAUNCH(4, 4) : p.bm == 128 ? W_LAUNCH(4, 2) : W_LAUNCH(2, 2);
+#undef W_LAUNCH
   if (rc) return rc;
-  return svlm_gemm_reduce_launch(partial, splits, bias, residual, ldr, C, ldc, M, N, act, norm_w, norm_b, eps, XN, ldxn, stream);
+  return svlm_gemm_reduce_launch(partial, p.splits, bias, residual, ldr, C, ldc, M, N, act, norm_w, norm_b, eps, XN, ldxn, stream);
 }
 
 extern "C" int svlm_gemm_wfp8(const void* A, int lda, const void* W8, int ldw, const float* w_scale, const void* bias, const void* residual,

@@ -39,10 +39,7 @@ def plan_mx(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
             splits = v
     if norm and splits == 1 and can_split and K >= 256 and 2 * M * N * 4 <= ws_bytes and N <= 4096:
         splits = 2
-    kps = K
-    if splits > 1:
-        kps = _cdiv(_cdiv(K, splits), 128) * 128
-        splits = _cdiv(K, kps)
+    splits, kps = G._finish_split(K, 128, splits)
     return dict(fp8=4, bm=bm, waves=4, stages=3, dma=1, splits=splits, kps=kps, table=0,
                 norm_fused=int(bool(norm) and splits > 1 and N <= 4096), kernel=KERNELS[bm])
 

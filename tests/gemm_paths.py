@@ -1,8 +1,8 @@
 """Python mirror of the GEMM dispatch (gemm_impl in csrc/gemm.hip, gemm_fp8_impl in csrc/gemm_fp8.hip), the operand generators and the
 case list of tests/test_gemm_paths_gpu.py (test helper, not product; needs no GPU).
 
-The mirror restates the cost model, the tuned table, the large-M rules and the tuning switches line by line, so that every case can
-name the kernel it expects in its id and the GPU test can assert that the diagnostic library reports exactly that plan.  A dispatch
+The mirror restates the cost model, the tuned table, the large-M rules and the tuning switches line by line (the pieces the GEMMs share
+in csrc/gemm_plan.h once: _cost_plan, _large_m_bm, _finish_split, plan_wcode), so that every case can name the kernel it expects in its id and the GPU test can assert that the diagnostic library reports exactly that plan.  A dispatch
 edit that is not mirrored here fails tests/test_gemm_ref64.py::test_mirror_matches_the_library_plan without a GPU."""
 from __future__ import annotations
 
@@ -41,11 +41,8 @@ def _cdiv(a, b):
     return (a + b - 1) // b
 
 
-def plan_bf16(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
-    """-> dict(fp8, bm, waves, stages, dma, splits, kps, table, norm_fused, kernel).  N = output columns (SwiGLU: I)."""
-    env = env or {}
-    swiglu = act == 4
-    gn = _cdiv(N, 64) if swiglu else _cdiv(N, 128)
+def _cost_plan(M, N, K, gn, ws_bytes):
+    """gemm_cost_plan (csrc/gemm_plan.h) -> (bm, splits)"""
     best_bm, best_splits, best_cost = 64, 1, 1e30
     for bm_c in (64, 128):
         if bm_c == 128 and M <= 64:
@@ -64,6 +61,67 @@ def plan_bf16(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
             cost = rounds * ksteps * step_us + slab_us
             if cost < best_cost:
                 best_cost, best_bm, best_splits = cost, bm_c, sp
+    return best_bm, best_splits
+
+
+def _large_m_bm(M, gn):
+    """gemm_large_m_bm (csrc/gemm_plan.h)"""
+    t256 = _cdiv(M, 256) * gn
+    rounds = (t256 + 255) // 256
+    return 256 if t256 * 100 >= rounds * 256 * 85 else 128
+
+
+def _finish_split(K, bk, splits):
+    """gemm_finish_split (csrc/gemm_plan.h) -> (splits, kps)"""
+    if splits <= 1:
+        return splits, K
+    kps = _cdiv(_cdiv(K, splits), bk) * bk
+    return _cdiv(K, kps), kps
+
+
+# (mb, N, K, bm, splits) -- kPlans of gemm_wcode_plan (csrc/gemm_plan.h)
+WCODE_TUNED = [(5, 1536, 8960, 64, 4), (5, 4608, 3584, 64, 2), (5, 3584, 3584, 64, 3), (5, 3584, 18944, 128, 8), (10, 3584, 18944, 128, 3),
+               (10, 18944, 3584, 128, 1), (5, 2560, 2048, 64, 3), (5, 2048, 2048, 64, 3), (5, 2048, 11008, 64, 4)]
+
+
+def plan_wcode(prefix, kind, kernels, M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
+    """gemm_wcode_plan (csrc/gemm_plan.h), the plan of the weight-code GEMMs -> dict(fp8=kind, bm, waves, stages, dma, splits, kps,
+    table, norm_fused, kernel).  prefix: of the switch names; kernels: {tile rows: kernel name}; N = output columns (SwiGLU: I)."""
+    env = env or {}
+    swiglu = act == 4
+    gn = _cdiv(N, 64) if swiglu else _cdiv(N, 128)
+    best_bm, best_splits = _cost_plan(M, N, K, gn, ws_bytes)
+    table = False
+    if prefix + "_NO_TABLE" not in env:
+        mb = _cdiv(M, 64)
+        for (pmb, pN, pK, pbm, psp) in WCODE_TUNED:
+            if pN == N and pK == K and pmb - 1 <= mb <= pmb + 1 and (psp == 1 or psp * M * N * 4 <= ws_bytes):
+                best_bm, best_splits, table = pbm, psp, True
+                break
+    if M >= 2048 and K >= 2048 and best_splits == 1:
+        best_bm = _large_m_bm(M, gn)
+    if prefix + "_BM" in env:
+        fb = int(env[prefix + "_BM"])
+        best_bm = fb if fb in (128, 256) else 64
+        table = False
+        fs = int(env.get(prefix + "_SPLITS", "0"))
+        best_splits = fs if fs > 0 else 1
+        if best_splits * M * N * 4 > ws_bytes or K < 1024:
+            best_splits = 1
+    if swiglu:
+        best_splits = 1
+    bm = best_bm
+    splits, kps = _finish_split(K, 64, best_splits)
+    return dict(fp8=kind, bm=bm, waves=8 if bm == 256 else 4, stages=3, dma=1, splits=splits, kps=kps, table=int(table),
+                norm_fused=int(bool(norm) and splits > 1 and N <= 4096), kernel=kernels[bm])
+
+
+def plan_bf16(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
+    """-> dict(fp8, bm, waves, stages, dma, splits, kps, table, norm_fused, kernel).  N = output columns (SwiGLU: I)."""
+    env = env or {}
+    swiglu = act == 4
+    gn = _cdiv(N, 64) if swiglu else _cdiv(N, 128)
+    best_bm, best_splits = _cost_plan(M, N, K, gn, ws_bytes)
     plan_w8 = plan_ns2 = table = False
     if "SVLM_GEMM_NO_TABLE" not in env:
         mb = _cdiv(M, 64)
@@ -73,9 +131,7 @@ def plan_bf16(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
                 break
     dma = K % 64 == 0 and "SVLM_GEMM_NO_DMA" not in env
     if dma and M >= 2048 and K >= 2048 and best_splits == 1 and "SVLM_GEMM_NO_T128" not in env:
-        t256 = _cdiv(M, 256) * gn
-        rounds = (t256 + 255) // 256
-        best_bm = 256 if t256 * 100 >= rounds * 256 * 85 else 128
+        best_bm = _large_m_bm(M, gn)
     if "SVLM_GEMM_BM" in env:
         fb = int(env["SVLM_GEMM_BM"])
         best_bm = fb if fb in (192, 320, 256) else (128 if fb == 128 and M > 64 else 64)
@@ -88,10 +144,8 @@ def plan_bf16(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
         best_splits = 1
         if best_bm > 128 and best_bm != 256:
             best_bm = 128
-    bm, splits, kps = best_bm, best_splits, K
-    if splits > 1:
-        kps = _cdiv(_cdiv(K, splits), 64) * 64
-        splits = _cdiv(K, kps)
+    bm = best_bm
+    splits, kps = _finish_split(K, 64, best_splits)
     if not dma and (bm in (192, 320, 256) or swiglu):
         raise ValueError("tall tiles and SwiGLU need the LDS-DMA kernel")
     small = bm == 64
@@ -134,10 +188,7 @@ def plan_fp8(M, N, K, norm=False, env=None, ws_bytes=WS_BYTES):
         bm = int(env["SVLM_GEMM8_BM"])
     if norm and splits == 1 and K >= 1024 and 2 * M * N * 4 <= ws_bytes and N <= 4096:
         splits = 2
-    kps = K
-    if splits > 1:
-        kps = _cdiv(_cdiv(K, splits), 128) * 128
-        splits = _cdiv(K, kps)
+    splits, kps = _finish_split(K, 128, splits)
     return dict(fp8=1, bm=bm, waves=4, stages=3, dma=1, splits=splits, kps=kps, table=0,
                 norm_fused=int(bool(norm) and splits > 1 and N <= 4096), kernel="fp8<2,3>" if bm == 64 else "fp8<4,3>")
 

@@ -1,67 +1,18 @@
-"""Python mirror of the weight-fp8 GEMM's dispatch (gemm_wfp8_impl in csrc/gemm_wfp8.hip) and the case list of
+"""Python mirror of the weight-fp8 GEMM's dispatch (gemm_wfp8_impl in csrc/gemm_wfp8.hip, planned by gemm_wcode_plan of csrc/gemm_plan.h) and the case list of
 tests/test_gemm_wfp8_gpu.py (test helper, not product; needs no GPU).  Operand generators and the bf16 mirror: tests/gemm_paths.py."""
 from __future__ import annotations
 
 import gemm_paths as G
 
 WS_BYTES = G.WS_BYTES
-# (mb, N, K, bm, splits) -- kPlans of gemm_wfp8.hip
-TUNED = [(5, 1536, 8960, 64, 4), (5, 4608, 3584, 64, 2), (5, 3584, 3584, 64, 3), (5, 3584, 18944, 128, 8), (10, 3584, 18944, 128, 3),
-         (10, 18944, 3584, 128, 1), (5, 2560, 2048, 64, 3), (5, 2048, 2048, 64, 3), (5, 2048, 11008, 64, 4)]
+TUNED = G.WCODE_TUNED          # the table of gemm_wcode_plan (csrc/gemm_plan.h)
 KERNELS = {64: "wfp8<2,3>", 128: "wfp8<4,3>", 256: "wfp8<4,3,4>"}
 _cdiv = G._cdiv
 
 
 def plan_wfp8(M, N, K, act=0, norm=False, env=None, ws_bytes=WS_BYTES):
     """-> dict(fp8=2, bm, waves, stages, dma, splits, kps, table, norm_fused, kernel).  N = output columns (SwiGLU: I)."""
-    env = env or {}
-    swiglu = act == 4
-    gn = _cdiv(N, 64) if swiglu else _cdiv(N, 128)
-    best_bm, best_splits, best_cost = 64, 1, 1e30
-    for bm_c in (64, 128):
-        if bm_c == 128 and M <= 64:
-            continue
-        tiles_c = _cdiv(M, bm_c) * gn
-        cap = 256 * (3 if bm_c == 64 else 2)
-        max_s = (min(K // 512, 16) if K >= 1024 else 1)
-        for sp in range(1, max_s + 1):
-            if sp > 1 and sp * M * N * 4 > ws_bytes:
-                break
-            wgs = tiles_c * sp
-            rounds = float((wgs + cap - 1) // cap)
-            ksteps = float((K + sp - 1) // sp + 63) / 64 + 3.0
-            step_us = 0.9 if bm_c == 64 else 1.5
-            slab_us = (2.0 * sp * M * N * 4.0 / 3e12 * 1e6 + 5.0) if sp > 1 else 0.0
-            cost = rounds * ksteps * step_us + slab_us
-            if cost < best_cost:
-                best_cost, best_bm, best_splits = cost, bm_c, sp
-    table = False
-    if "SVLM_GEMM_WFP8_NO_TABLE" not in env:
-        mb = _cdiv(M, 64)
-        for (pmb, pN, pK, pbm, psp) in TUNED:
-            if pN == N and pK == K and pmb - 1 <= mb <= pmb + 1 and (psp == 1 or psp * M * N * 4 <= ws_bytes):
-                best_bm, best_splits, table = pbm, psp, True
-                break
-    if M >= 2048 and K >= 2048 and best_splits == 1:
-        t256 = _cdiv(M, 256) * gn
-        rounds = (t256 + 255) // 256
-        best_bm = 256 if t256 * 100 >= rounds * 256 * 85 else 128
-    if "SVLM_GEMM_WFP8_BM" in env:
-        fb = int(env["SVLM_GEMM_WFP8_BM"])
-        best_bm = fb if fb in (128, 256) else 64
-        table = False
-        fs = int(env.get("SVLM_GEMM_WFP8_SPLITS", "0"))
-        best_splits = fs if fs > 0 else 1
-        if best_splits * M * N * 4 > ws_bytes or K < 1024:
-            best_splits = 1
-    if swiglu:
-        best_splits = 1
-    bm, splits, kps = best_bm, best_splits, K
-    if splits > 1:
-        kps = _cdiv(_cdiv(K, splits), 64) * 64
-        splits = _cdiv(K, kps)
-    return dict(fp8=2, bm=bm, waves=8 if bm == 256 else 4, stages=3, dma=1, splits=splits, kps=kps, table=int(table),
-                norm_fused=int(bool(norm) and splits > 1 and N <= 4096), kernel=KERNELS[bm])
+    return G.plan_wcode("SVLM_GEMM_WFP8", 2, KERNELS, M, N, K, act=act, norm=norm, env=env, ws_bytes=ws_bytes)
 
 
 def _case(M, N, K, gen="iid", bias=False, res=False, act=0, force=None, ld=False, norm=None, inplace=False, note=""):
