@@ -1,4 +1,5 @@
-// MXFP4 weight-stream pieces of the fp4 decode kernels (decode_fp4.hip): OCP e2m1 codes, two per byte (element 2i in the low nibble of
+// MXFP4 weight-stream pieces shared by the single-row (decode_fp4.hip) and the lane-batched (decode_batch_fp4.hip) fp4 decode kernels,
+// with the format policy WFp4 of the kernel shells (dec_shell.h): OCP e2m1 codes, two per byte (element 2i in the low nibble of
 // byte i), one e8m0 scale byte per block of 32 consecutive K elements in an array of its own (row-major, K / 32 per row).  A K-step is
 // 2048 elements, 32 consecutive ones per lane: one 16-B load = 32 codes = exactly one block, so a lane needs one scale byte per load.
 #pragma once
@@ -55,3 +56,43 @@ __device__ __forceinline__ void preload_w4(const fp4x2_t* const (&wr)[NR], const
     }
   }
 }
+
+// the K loops, defined where they are used: the single-row one in decode_fp4.hip, the lane-batched one in decode_batch_fp4.hip
+template <int NR, int PRE>
+__device__ __forceinline__ void wave_dots4(const fp4x2_t* const (&wr)[NR], const e8m0_t* const (&sr)[NR], const bf16_t* xs, int K,
+                                           float (&acc)[NR], W4Pre<NR, PRE>& pre);
+template <int NB, int NR, int PRE>
+__device__ __forceinline__ void wave_dots4_b(const fp4x2_t* const (&wr)[NR], const e8m0_t* const (&sr)[NR], const bf16_t* xs, int K,
+                                             float (&acc)[NB][NR], W4Pre<NR, PRE>& pre);
+
+// format policy (see WBf16, dec_stream.h).  MXFP4: a row is its code pointer plus the pointer to its K / 32 scale bytes; the scales
+// are applied inside the K loop's conversion, so there is no row scale.
+struct WFp4 {
+  typedef fp4x2_t w_t;
+  typedef e8m0_t s_t;
+  static constexpr bool row_scale = false;
+  template <int NR>
+  struct Rows {
+    const fp4x2_t* w[NR];
+    const e8m0_t* s[NR];
+  };
+  template <int NR, int PRE>
+  using Pre = W4Pre<NR, PRE>;
+  template <int NR>
+  static __device__ __forceinline__ void row(Rows<NR>& R, int r, const w_t* W, int ldw, const s_t* S, int n, int K) {
+    R.w[r] = W + (size_t)n * ldw;
+    R.s[r] = S + (size_t)n * (K >> 5);
+  }
+  template <int NR, int PRE>
+  static __device__ __forceinline__ void preload(const Rows<NR>& R, int base, int K, Pre<NR, PRE>& pre) {
+    preload_w4<NR, PRE>(R.w, R.s, base, K, pre);
+  }
+  template <int NR, int PRE>
+  static __device__ __forceinline__ void dots(const Rows<NR>& R, const bf16_t* xs, int K, float (&acc)[NR], Pre<NR, PRE>& pre) {
+    wave_dots4<NR, PRE>(R.w, R.s, xs, K, acc, pre);
+  }
+  template <int NB, int NR, int PRE>
+  static __device__ __forceinline__ void dots_b(const Rows<NR>& R, const bf16_t* xs, int K, float (&acc)[NB][NR], Pre<NR, PRE>& pre) {
+    wave_dots4_b<NB, NR, PRE>(R.w, R.s, xs, K, acc, pre);
+  }
+};

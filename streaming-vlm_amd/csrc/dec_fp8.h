@@ -1,6 +1,7 @@
 // e4m3 weight-stream pieces shared by the single-row (decode_fp8.hip) and the lane-batched (decode_batch_fp8.hip) fp8 decode
-// kernels: the activation fetch of one lane's K-step, the 16-element dot product in element order, and the pre-issued head of a
-// wave's weight rows.  A K-step is 1024 elements, 16 consecutive ones per thread (one 16-B load = 16 codes).
+// kernels: the activation fetch of one lane's K-step, the 16-element dot product in element order, the pre-issued head of a
+// wave's weight rows, and the format policy WFp8 of the kernel shells (dec_shell.h).  A K-step is 1024 elements, 16 consecutive ones
+// per thread (one 16-B load = 16 codes).  x16 and f32x2_t also serve the fp4 kernels (dec_fp4.h).
 #pragma once
 #include "common.h"
 
@@ -51,3 +52,35 @@ __device__ __forceinline__ void preload_w8(const fp8_t* const (&wr)[NR], int bas
     for (int r = 0; r < NR; ++r) pre.w[it][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr[r] + cc));
   }
 }
+
+// the K loops, defined where they are used: the single-row one in decode_fp8.hip, the lane-batched one in decode_batch_fp8.hip
+template <int NR, int PRE>
+__device__ __forceinline__ void wave_dots8(const fp8_t* const (&wr)[NR], const bf16_t* xs, int K, float (&acc)[NR], W8Pre<NR, PRE>& pre);
+template <int NB, int NR, int PRE>
+__device__ __forceinline__ void wave_dots8_b(const fp8_t* const (&wr)[NR], const bf16_t* xs, int K, float (&acc)[NB][NR], W8Pre<NR, PRE>& pre);
+
+// format policy (see WBf16, dec_stream.h).  e4m3: a row is its code pointer; its scale S[n] is fetched by the shell with the row's
+// index and multiplied in once, in the epilogue.
+struct WFp8 {
+  typedef fp8_t w_t;
+  typedef float s_t;                  // one power-of-two scale per output row
+  static constexpr bool row_scale = true;
+  template <int NR>
+  struct Rows {
+    const fp8_t* w[NR];
+  };
+  template <int NR, int PRE>
+  using Pre = W8Pre<NR, PRE>;
+  template <int NR>
+  static __device__ __forceinline__ void row(Rows<NR>& R, int r, const w_t* W, int ldw, const s_t*, int n, int) { R.w[r] = W + (size_t)n * ldw; }
+  template <int NR, int PRE>
+  static __device__ __forceinline__ void preload(const Rows<NR>& R, int base, int K, Pre<NR, PRE>& pre) { preload_w8<NR, PRE>(R.w, base, K, pre); }
+  template <int NR, int PRE>
+  static __device__ __forceinline__ void dots(const Rows<NR>& R, const bf16_t* xs, int K, float (&acc)[NR], Pre<NR, PRE>& pre) {
+    wave_dots8<NR, PRE>(R.w, xs, K, acc, pre);
+  }
+  template <int NB, int NR, int PRE>
+  static __device__ __forceinline__ void dots_b(const Rows<NR>& R, const bf16_t* xs, int K, float (&acc)[NB][NR], Pre<NR, PRE>& pre) {
+    wave_dots8_b<NB, NR, PRE>(R.w, xs, K, acc, pre);
+  }
+};

@@ -1,8 +1,11 @@
-// The lane table and the activation-row prologue shared by the lane-batched decode kernels (decode_batch.hip: bf16 weights,
-// decode_batch_fp8.hip: e4m3 weights).
+// What the lane-batched decode kernels share whatever their weights: the lane table and its side tables, the activation-row prologue,
+// and a lane's KV append.  Included by decode_batch.hip (bf16), decode_batch_fp8.hip (e4m3),
+// decode_batch_fp4.hip (MXFP4), decode_wide.hip (MFMA, bf16) and decode_attn.hip (svlm_decb_attn); the kernel shells of the first three
+// are in dec_shell.h.
 #pragma once
 #include "common.h"
 #include "dec_xrow.h"
+#include "dec_epi.h"
 
 struct svlm_lane {                 // mirror of include/svlm.h
   bf16_t* pool;                    // [n_layers][2][Hkv][n_slots][D]
@@ -49,6 +52,16 @@ void decb_embed_launch(const void* lanes, int B, const void* table, int n_rows, 
 void decb_argmax_finish_launch(const void* lanes, int B, const void* ws, int V, int advance_kv, void* stream);
 
 __device__ __forceinline__ bool lane_live(const svlm_lane& L) { return L.state[1] + 1 < L.limit; }
+
+// kv_append (dec_epi.h) for a lane: column j of the [k | v] output of the lane's new token at logical row `row`, into the planes of
+// `layer` in the lane's own pool and, if it has them, linear planes.  Only the base of the plane column j belongs to is computed (it
+// stands for both of kv_append's bases).
+__device__ __forceinline__ void lane_kv_append(const svlm_lane& L, int layer, int Hkv, int D, int row, int slot, int j, int kd, bf16_t v) {
+  const int p = layer * 2 + (j < kd ? 0 : 1);
+  bf16_t* plane = L.pool + (size_t)p * Hkv * L.n_slots * D;
+  bf16_t* lp = L.lin != nullptr ? L.lin + (size_t)p * Hkv * L.lin_rows * D : nullptr;
+  kv_append(plane, plane, L.n_slots, lp, lp, L.lin_rows, row, slot, j, kd, D, v);
+}
 
 // Prologue of the fused kernels: the live lanes' x rows are requested first, then the head of the weight stream, then the rows are
 // normalised and staged one after the other (xs[b * K ..]); a lane that is not live leaves its LDS row as it is (its products are

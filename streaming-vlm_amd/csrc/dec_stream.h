@@ -1,5 +1,6 @@
-// Pieces of the weight-streaming decode kernels shared by the single-row (decode_fused.hip) and the lane-batched (decode_batch.hip)
-// forms: the pre-issued head of a wave's weight rows, and the winner-over-candidates + token feedback of svlm_argmax_finish.
+// bf16 weight-stream pieces of the decode kernels, shared by the single-row (decode_fused.hip) and the lane-batched (decode_batch.hip)
+// forms: the pre-issued head of a wave's weight rows, the bf16 format policy WBf16 of the kernel shells
+// (dec_shell.h), and the winner-over-candidates + token feedback of svlm_argmax_finish.
 #pragma once
 #include "common.h"
 
@@ -21,6 +22,40 @@ __device__ __forceinline__ void preload_w(const bf16_t* const (&wr)[NR], int bas
     for (int r = 0; r < NR; ++r) pre.w[it][r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr[r] + cc));
   }
 }
+
+// The K loops of the bf16 weight stream, defined where they are used: the single-row one in decode_fused.hip, the lane-batched one in
+// decode_batch.hip.
+template <int NR, int PRE>
+__device__ __forceinline__ void wave_dots(const bf16_t* const (&wr)[NR], const bf16_t* xs, int K, float (&acc)[NR], WPre<NR, PRE>& pre);
+template <int NB, int NR, int PRE>
+__device__ __forceinline__ void wave_dots_b(const bf16_t* const (&wr)[NR], const bf16_t* xs, int K, float (&acc)[NB][NR], WPre<NR, PRE>& pre);
+
+// WEIGHT-FORMAT POLICY of the kernel shells (dec_shell.h).  A policy only NAMES what a format has -- the kernel-argument types, the
+// handles of a wave's NR rows, the pre-issued registers, the preload and the two K loops -- and has no arithmetic of its own.
+// bf16: a row is its pointer; no scale.
+struct WBf16 {
+  typedef bf16_t w_t;                 // the weight argument
+  typedef void s_t;                   // the scale argument (none)
+  static constexpr bool row_scale = false;
+  template <int NR>
+  struct Rows {
+    const bf16_t* w[NR];
+  };
+  template <int NR, int PRE>
+  using Pre = WPre<NR, PRE>;
+  template <int NR>
+  static __device__ __forceinline__ void row(Rows<NR>& R, int r, const w_t* W, int ldw, const s_t*, int n, int) { R.w[r] = W + (size_t)n * ldw; }
+  template <int NR, int PRE>
+  static __device__ __forceinline__ void preload(const Rows<NR>& R, int base, int K, Pre<NR, PRE>& pre) { preload_w<NR, PRE>(R.w, base, K, pre); }
+  template <int NR, int PRE>
+  static __device__ __forceinline__ void dots(const Rows<NR>& R, const bf16_t* xs, int K, float (&acc)[NR], Pre<NR, PRE>& pre) {
+    wave_dots<NR, PRE>(R.w, xs, K, acc, pre);
+  }
+  template <int NB, int NR, int PRE>
+  static __device__ __forceinline__ void dots_b(const Rows<NR>& R, const bf16_t* xs, int K, float (&acc)[NB][NR], Pre<NR, PRE>& pre) {
+    wave_dots_b<NB, NR, PRE>(R.w, xs, K, acc, pre);
+  }
+};
 
 // winner over the per-workgroup candidates of a dec_lm_head launch + device-side token feedback; one 1024-thread workgroup
 __device__ __forceinline__ void argmax_finish_body(const float* __restrict__ part_val, const int* __restrict__ part_idx, int n_parts,

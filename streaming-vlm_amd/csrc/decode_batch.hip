@@ -13,6 +13,11 @@
 //   svlm_decb_sample_finish  one workgroup per lane: svlm_argmax_finish over the candidates (greedy, Gumbel) or the top-k / top-p
 //                            draw of svlm_penalty_sample on the lane's own logits row (dec_sample.h)
 //
+// The fused kernels are the lane-batched shells of dec_shell.h over the policy WBf16 (dec_stream.h), shared with decode_batch_fp8.hip
+// and decode_batch_fp4.hip, around this file's K loop (fma_batch_b, wave_dots_b); their epilogue pieces (KV append, candidate scoring and
+// reduce, residual tail) are those of the single-row kernels, in dec_epi.h.  The residual GEMVs, the embedding gather and the finish
+// kernels are this file's own.
+//
 // Each wave loads its weight rows once (the same 16-B non-temporal loads and PRE run-ahead as decode_fused.hip) and multiplies them
 // with the NB activation rows of the group.  The fused kernels stage the NB normalised rows in LDS; svlm_decb_gemv reads its NB
 // un-normalised rows straight from global memory like svlm_gemv_bf16 does (a down_proj row of 4 lanes is 150 KB: it does not fit a
@@ -29,7 +34,9 @@
 #include "common.h"
 #include "dec_xrow.h"
 #include "dec_stream.h"
-#include "dec_lanes.h"            // svlm_lane, lane_live, load_rows, stage_rows: shared with decode_batch_fp8.hip
+#include "dec_lanes.h"            // svlm_lane, lane_live, load_rows, stage_rows, DECB_SWITCH_NB: shared by all lane-batched files
+#include "dec_launch.h"           // host side: lane-count switch, qkv argument checks
+#include "dec_shell.h"            // the kernel shells over WBf16 (dec_stream.h); epilogue pieces: dec_epi.h
 #include "dec_sample.h"
 
 // acc[b][r] += W[row r] . xs[b] over the PRE K-steps held in `pre`; per (b, r) the same FMA sequence as fma_batch (decode_fused.hip)
@@ -95,47 +102,7 @@ __global__ __launch_bounds__(256) void decb_qkv_kernel(const svlm_lane* __restri
                                                        const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
                                                        const bf16_t* __restrict__ bias, bf16_t* __restrict__ q_out, int ldq, int layer,
                                                        int N, int K, int qd, int kd, int D) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wave;
-  const bf16_t* wr[1] = {W + (size_t)min(n, N - 1) * ldw};
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  WPre<1, PRE> pre;
-  preload_w<1, PRE>(wr, 0, K, pre);
-  const bf16_t bpre = bias[min(n, N - 1)];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  if (n >= N) return;
-  float acc[NB][1];
-  wave_dots_b<NB, 1, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-    const int Hkv = kd / D;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const svlm_lane& L = lanes[b];
-      const bf16_t v = f2bf(acc[b][0] + bf2f(bpre));
-      if (n < qd) {
-        q_out[(size_t)b * ldq + n] = v;
-      } else {
-        const int row = L.state[0];
-        const int slot = L.slot_of[row];
-        const int j = n - qd;
-        const int jj = j < kd ? j : j - kd;
-        const int h = jj / D, d = jj % D;
-        bf16_t* plane = L.pool + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.n_slots * D;
-        plane[((size_t)h * L.n_slots + slot) * D + d] = v;
-        if (L.lin != nullptr) {      // as svlm_dec_qkv_lin: the key UN-rotated in its tile position, the value as it is, at logical row `row`
-          bf16_t* lp = L.lin + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.lin_rows * D;
-          if (j < kd) lp[((size_t)h * (L.lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-          else lp[((size_t)h * L.lin_rows + row) * D + d] = v;
-        }
-      }
-    }
-  }
+  decb_qkv_body<WBf16, NB, PRE, XC>(lanes, x, ldx, ln_w, eps, W, ldw, /* S: none */ nullptr, bias, q_out, ldq, layer, N, K, qd, kd, D);
 }
 
 // ---------------------------------------------------------------- gate/up + SwiGLU
@@ -143,114 +110,19 @@ template <int NB, int PRE, int XC>
 __global__ __launch_bounds__(256) void decb_gate_up_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
                                                            const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
                                                            bf16_t* __restrict__ h, int ldh, int I, int K) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wave;
-  const int nc = min(n, I - 1);
-  const bf16_t* wr[2] = {W + (size_t)nc * ldw, W + (size_t)(I + nc) * ldw};       // gate row n, up row n
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  WPre<2, PRE> pre;
-  preload_w<2, PRE>(wr, 0, K, pre);
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  if (n >= I) return;
-  float acc[NB][2];
-  wave_dots_b<NB, 2, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const float g = rbf(acc[b][0]), u = rbf(acc[b][1]);
-      h[(size_t)b * ldh + n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
-    }
-  }
+  decb_gate_up_body<WBf16, NB, PRE, XC>(lanes, x, ldx, ln_w, eps, W, ldw, /* S: none */ nullptr, h, ldh, I, K);
 }
 
 // ---------------------------------------------------------------- lm_head + penalty + argmax candidates
 #define DECB_LM_ROWS 2            // = LM_ROWS of decode_fused.hip: the candidates are per workgroup of 4 x LM_ROWS vocabulary rows
-// SMP: a live lane whose sampling record says Gumbel gets score * inv_temp + noise(seed, token index, vocabulary index) as its candidate
-// score, the expression of dec_lm_head_kernel (decode_fused.hip); the logits row and the other lanes' candidates do not change.
-template <int NB, int PRE, int XC, bool SMP>
-__device__ __forceinline__ void decb_lm_head_body(const svlm_lane* __restrict__ lanes, const svlm_lane_sample* __restrict__ samples,
-                                                  const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ ln_w, float eps,
-                                                  const bf16_t* __restrict__ W, int ldw, float* __restrict__ logits, int ldl,
-                                                  const int* __restrict__ suppress, float* __restrict__ ws, long long ws_stride, int V, int K) {
-  constexpr int ROWS = DECB_LM_ROWS;
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const bf16_t* wr[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, V - 1) * ldw;
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  WPre<ROWS, PRE> pre;
-  preload_w<ROWS, PRE>(wr, 0, K, pre);
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  float best[NB];
-  int bi[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) { best[b] = -INFINITY; bi[b] = 0x7fffffff; }
-  if (n0 < V) {
-    float acc[NB][ROWS];
-    wave_dots_b<NB, ROWS, PRE>(wr, xs, K, acc, pre);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const svlm_lane& L = lanes[b];
-      const unsigned* rng = nullptr;
-      float inv_temp = 1.0f;
-      if constexpr (SMP) {
-        if (samples[b].mode == SVLM_SAMPLE_GUMBEL) { rng = samples[b].rng; inv_temp = samples[b].inv_temp; }
-      }
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const int n = n0 + r;
-        if (n >= V) break;
-        float v = rbf(acc[b][r]);
-        if (lane == 0) logits[(size_t)b * ldl + n] = v;
-        if (L.seen && L.seen[n]) v = v < 0.f ? v * L.penalty : v / L.penalty;
-        for (int s = 0; s < L.n_suppress; ++s)
-          if (suppress[s] == n) v = -INFINITY;
-        if constexpr (SMP) {
-          if (rng) v = v * inv_temp + svlm_gumbel_noise(rng, (unsigned)(L.state[1] + 1), (unsigned)n);
-        }
-        if (v > best[b] || (v == best[b] && n < bi[b])) { best[b] = v; bi[b] = n; }
-      }
-    }
-  }
-  __shared__ float sb[NB][4];
-  __shared__ int si[NB][4];
-  if (lane == 0) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) { sb[b][wave] = best[b]; si[b][wave] = bi[b]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < NB && lane_live(lanes[threadIdx.x])) {
-    const int b = threadIdx.x;
-    float bb = sb[b][0];
-    int ii = si[b][0];
-    for (int w = 1; w < 4; ++w)
-      if (sb[b][w] > bb || (sb[b][w] == bb && si[b][w] < ii)) { bb = sb[b][w]; ii = si[b][w]; }
-    float* pv = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (size_t)b * ws_stride);
-    int* pi = reinterpret_cast<int*>(pv + gridDim.x);
-    pv[blockIdx.x] = bb;
-    pi[blockIdx.x] = ii;
-  }
-}
-
+// (SMP, the Gumbel candidates of svlm_decb_lm_head_sample: decb_lm_head_body, dec_shell.h)
 template <int NB, int PRE, int XC>
 __global__ __launch_bounds__(256) void decb_lm_head_kernel(const svlm_lane* __restrict__ lanes, const bf16_t* __restrict__ x, int ldx,
                                                            const bf16_t* __restrict__ ln_w, float eps, const bf16_t* __restrict__ W, int ldw,
                                                            float* __restrict__ logits, int ldl, const int* __restrict__ suppress,
                                                            float* __restrict__ ws, long long ws_stride, int V, int K) {
-  decb_lm_head_body<NB, PRE, XC, false>(lanes, nullptr, x, ldx, ln_w, eps, W, ldw, logits, ldl, suppress, ws, ws_stride, V, K);
+  decb_lm_head_body<WBf16, NB, DECB_LM_ROWS, PRE, XC, false>(lanes, nullptr, x, ldx, ln_w, eps, W, ldw, /* S: none */ nullptr, logits, ldl, suppress, ws, ws_stride,
+                                                             V, K);
 }
 
 template <int NB, int PRE, int XC>
@@ -260,7 +132,8 @@ __global__ __launch_bounds__(256) void decb_lm_head_sample_kernel(const svlm_lan
                                                                   const bf16_t* __restrict__ W, int ldw, float* __restrict__ logits, int ldl,
                                                                   const int* __restrict__ suppress, float* __restrict__ ws,
                                                                   long long ws_stride, int V, int K) {
-  decb_lm_head_body<NB, PRE, XC, true>(lanes, samples, x, ldx, ln_w, eps, W, ldw, logits, ldl, suppress, ws, ws_stride, V, K);
+  decb_lm_head_body<WBf16, NB, DECB_LM_ROWS, PRE, XC, true>(lanes, samples, x, ldx, ln_w, eps, W, ldw, /* S: none */ nullptr, logits, ldl, suppress, ws, ws_stride,
+                                                            V, K);
 }
 
 __global__ __launch_bounds__(1024) void decb_argmax_finish_kernel(const svlm_lane* __restrict__ lanes, const float* __restrict__ ws,
@@ -366,10 +239,7 @@ __global__ __launch_bounds__(256) void decb_gemv_kernel(const svlm_lane* __restr
       for (int r = 0; r < ROWS; ++r) {
         const int n = n0 + r;
         if (n >= N) break;
-        float v = acc[b][r] + 0.f;                       // (the single-row kernel's "+ no bias": -0 becomes +0 there too)
-        v = rbf(v);
-        v = rbf(v + bf2f(epi_raw[b][r]));
-        y[(size_t)b * ldy + n] = f2bf(v);
+        y[(size_t)b * ldy + n] = resid_tail(acc[b][r], epi_raw[b][r]);
       }
     }
   }
@@ -443,10 +313,7 @@ __global__ __launch_bounds__(256) void decb_gemv_ksplit_kernel(const svlm_lane* 
   if (threadIdx.x < NB * ROWS) {
     const int n = n0 + er;
     if (n < N && lane_live(lanes[eb])) {
-      float v = part[0][eb][er] + part[1][eb][er] + part[2][eb][er] + part[3][eb][er] + 0.f;
-      v = rbf(v);
-      v = rbf(v + bf2f(epi_raw));
-      y[(size_t)eb * ldy + n] = f2bf(v);
+      y[(size_t)eb * ldy + n] = resid_tail(part[0][eb][er] + part[1][eb][er] + part[2][eb][er] + part[3][eb][er], epi_raw);
     }
   }
 }
@@ -462,21 +329,6 @@ static inline bool decb_ok(int B, int K, int ldx) { return B >= 1 && B <= 4 && K
     else if ((K) <= 4096) KERNEL<NB, 4, 2> __VA_ARGS__;                     \
     else KERNEL<NB, 4, 4> __VA_ARGS__;                                      \
   } while (0)
-#define DECB_DISPATCH(KERNEL, B, K, ...)                                    \
-  do {                                                                      \
-    if ((B) == 1) DECB_K(KERNEL, 1, K, __VA_ARGS__);                        \
-    else if ((B) == 2) DECB_K(KERNEL, 2, K, __VA_ARGS__);                   \
-    else if ((B) == 3) DECB_K(KERNEL, 3, K, __VA_ARGS__);                   \
-    else DECB_K(KERNEL, 4, K, __VA_ARGS__);                                 \
-  } while (0)
-#define DECB_ROWS(KERNEL, B, ROWS, ...)                                     \
-  do {                                                                      \
-    if ((B) == 1) KERNEL<1, ROWS> __VA_ARGS__;                              \
-    else if ((B) == 2) KERNEL<2, ROWS> __VA_ARGS__;                         \
-    else if ((B) == 3) KERNEL<3, ROWS> __VA_ARGS__;                         \
-    else KERNEL<4, ROWS> __VA_ARGS__;                                       \
-  } while (0)
-
 // The two launches whose geometry is one grid row / one workgroup PER LANE and nothing else of B: the entries below keep B <= 4, the
 // wide entries (decode_wide.hip) check 1..16 and launch the same kernels through these (declared in dec_lanes.h).
 void decb_embed_launch(const void* lanes, int B, const void* table, int n_rows, void* x, int ldx, int cols, void* stream) {
@@ -499,12 +351,11 @@ extern "C" int svlm_decb_embed(const void* lanes, int B, const void* table, int 
 extern "C" int svlm_decb_qkv(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W, int ldw,
                              const void* bias, void* q_out, int ldq, int layer, int K, int qd, int kd, int D, void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && decb_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0, "svlm_decb_qkv: bad B=%d K=%d ldx=%d ldw=%d", B, K, ldx, ldw);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D == 128 && kd % D == 0 && bias != nullptr && ldq >= qd && layer >= 0,
-                 "svlm_decb_qkv: bad qd=%d kd=%d D=%d ldq=%d layer=%d (head_dim 128)", qd, kd, D, ldq, layer);
+  if (!decb_qkv_args_ok("svlm_decb_qkv", qd, kd, D, bias, ldq, layer)) return SVLM_EINVAL;
   const int N = qd + 2 * kd;
-  DECB_DISPATCH(decb_qkv_kernel, B, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB_K(decb_qkv_kernel, NB, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, (const bf16_t*)bias, (bf16_t*)q_out, ldq,
-      layer, N, K, qd, kd, D));
+      layer, N, K, qd, kd, D)));
   return svlm_check_launch("svlm_decb_qkv");
 }
 
@@ -512,8 +363,8 @@ extern "C" int svlm_decb_gate_up(const void* lanes, int B, const void* x, int ld
                                  void* h, int ldh, int I, int K, void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && decb_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0 && I > 0 && ldh >= I,
                  "svlm_decb_gate_up: bad B=%d I=%d K=%d ldx=%d ldw=%d ldh=%d", B, I, K, ldx, ldw, ldh);
-  DECB_DISPATCH(decb_gate_up_kernel, B, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
-      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, (bf16_t*)h, ldh, I, K));
+  DECB_SWITCH_NB(B, DECB_K(decb_gate_up_kernel, NB, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, (bf16_t*)h, ldh, I, K)));
   return svlm_check_launch("svlm_decb_gate_up");
 }
 
@@ -524,15 +375,15 @@ extern "C" int svlm_decb_gemv(const void* lanes, int B, const void* x, int ldx, 
   SVLM_CHECK_ARG(residual != nullptr && y != nullptr && ldr >= N && ldy >= N, "svlm_decb_gemv: residual and y are required (ldr=%d ldy=%d)", ldr, ldy);
   hipStream_t s = (hipStream_t)stream;
   if (N <= 8192 && K >= 4096) {        // the shapes svlm_gemv_bf16 splits over K
-    DECB_ROWS(decb_gemv_ksplit_kernel, B, 2, <<<(N + 1) / 2, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
+    DECB_SWITCH_NB(B, decb_gemv_ksplit_kernel<NB, 2><<<(N + 1) / 2, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
                                                                         (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K));
     return svlm_check_launch("svlm_decb_gemv(ksplit)");
   }
   if (N >= 4096 || (long long)N * K >= (8LL << 20)) {
-    DECB_ROWS(decb_gemv_kernel, B, 2, <<<(N + 7) / 8, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
+    DECB_SWITCH_NB(B, decb_gemv_kernel<NB, 2><<<(N + 7) / 8, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
                                                                  (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K));
   } else {
-    DECB_ROWS(decb_gemv_kernel, B, 1, <<<(N + 3) / 4, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
+    DECB_SWITCH_NB(B, decb_gemv_kernel<NB, 1><<<(N + 3) / 4, 256, 0, s>>>((const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)W, ldw,
                                                                  (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K));
   }
   return svlm_check_launch("svlm_decb_gemv");
@@ -550,9 +401,9 @@ extern "C" int svlm_decb_lm_head(const void* lanes, int B, const void* x, int ld
                  "svlm_decb_lm_head: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d", B, V, K, ldx, ldw, ldl);
   SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head: null logits / workspace");
   const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
-  DECB_DISPATCH(decb_lm_head_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB_K(decb_lm_head_kernel, NB, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, logits, ldl, suppress, (float*)ws,
-      svlm_decb_lm_head_ws_stride(V), V, K));
+      svlm_decb_lm_head_ws_stride(V), V, K)));
   return svlm_check_launch("svlm_decb_lm_head");
 }
 
@@ -569,9 +420,9 @@ extern "C" int svlm_decb_lm_head_sample(const void* lanes, const void* samples, 
                  "svlm_decb_lm_head_sample: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d or no lane / sample table", B, V, K, ldx, ldw, ldl);
   SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head_sample: null logits / workspace");
   const int nb = (V + 4 * DECB_LM_ROWS - 1) / (4 * DECB_LM_ROWS);
-  DECB_DISPATCH(decb_lm_head_sample_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB_K(decb_lm_head_sample_kernel, NB, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const svlm_lane_sample*)samples, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const bf16_t*)W, ldw, logits,
-      ldl, suppress, (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K));
+      ldl, suppress, (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K)));
   return svlm_check_launch("svlm_decb_lm_head_sample");
 }
 

@@ -1,6 +1,7 @@
 // Lane-batched decode-step kernels on OCP MXFP4 weights (e2m1 codes, two per byte, one e8m0 scale per block of 32 K elements): stream
-// groups (stream_group.py) on an `llm_fp4` engine.  Each kernel is the lane-batched twin of one single-row fp4 kernel (decode_fp4.hip),
-// the relationship decode_batch_fp8.hip has to decode_fp8.hip:
+// groups (stream_group.py) on an `llm_fp4` engine.  The fused kernels are the lane-batched shells of dec_shell.h over the policy WFp4
+// (dec_fp4.h) around this file's K loop (cvt16_fp4, fma_batch4_b, wave_dots4_b), with the epilogue pieces of the single-row kernels
+// (dec_epi.h); the residual GEMV is this file's own, as in decode_batch_fp8.hip.  Entry, its single-row counterpart:
 //
 //   svlm_decb_qkv_fp4      svlm_dec_qkv_fp4       RMSNorm + QKV + bias + KV append to each lane's own pool slot / linear planes
 //   svlm_decb_gate_up_fp4  svlm_dec_gate_up_fp4   RMSNorm + gate/up + SwiGLU
@@ -25,6 +26,8 @@
 #include "dec_xrow.h"
 #include "dec_fp4.h"
 #include "dec_lanes.h"
+#include "dec_launch.h"           // host side: lane-count switch, qkv argument checks
+#include "dec_shell.h"            // the kernel shells over WFp4 (dec_fp4.h); epilogue pieces: dec_epi.h
 
 // the 16 codes of one half block (w0 | w1: 8 bytes) times the block scale, as fp32 in element order: the factors dot16_fp4 feeds its
 // FMAs with
@@ -114,49 +117,7 @@ __global__ __launch_bounds__(256) void decb_qkv_fp4_kernel(const svlm_lane* __re
                                                            const e8m0_t* __restrict__ S, const bf16_t* __restrict__ bias,
                                                            bf16_t* __restrict__ q_out, int ldq, int layer, int N, int K, int qd, int kd,
                                                            int D) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wave;
-  const int nc = min(n, N - 1);
-  const fp4x2_t* wr[1] = {W + (size_t)nc * ldw};
-  const e8m0_t* sr[1] = {S + (size_t)nc * (K >> 5)};
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  W4Pre<1, PRE> pre;
-  preload_w4<1, PRE>(wr, sr, 0, K, pre);
-  const bf16_t bpre = bias[nc];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  if (n >= N) return;
-  float acc[NB][1];
-  wave_dots4_b<NB, 1, PRE>(wr, sr, xs, K, acc, pre);
-  if (lane == 0) {
-    const int Hkv = kd / D;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const svlm_lane& L = lanes[b];
-      const bf16_t v = f2bf(acc[b][0] + bf2f(bpre));
-      if (n < qd) {
-        q_out[(size_t)b * ldq + n] = v;
-      } else {
-        const int row = L.state[0];
-        const int slot = L.slot_of[row];
-        const int j = n - qd;
-        const int jj = j < kd ? j : j - kd;
-        const int h = jj / D, d = jj % D;
-        bf16_t* plane = L.pool + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.n_slots * D;
-        plane[((size_t)h * L.n_slots + slot) * D + d] = v;
-        if (L.lin != nullptr) {      // the linear planes' layout of svlm_dec_qkv_lin, at logical row `row`
-          bf16_t* lp = L.lin + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.lin_rows * D;
-          if (j < kd) lp[((size_t)h * (L.lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-          else lp[((size_t)h * L.lin_rows + row) * D + d] = v;
-        }
-      }
-    }
-  }
+  decb_qkv_body<WFp4, NB, PRE, XC>(lanes, x, ldx, ln_w, eps, W, ldw, S, bias, q_out, ldq, layer, N, K, qd, kd, D);
 }
 
 // ---------------------------------------------------------------- gate/up + SwiGLU
@@ -165,31 +126,7 @@ __global__ __launch_bounds__(256) void decb_gate_up_fp4_kernel(const svlm_lane* 
                                                                const bf16_t* __restrict__ ln_w, float eps, const fp4x2_t* __restrict__ W,
                                                                int ldw, const e8m0_t* __restrict__ S, bf16_t* __restrict__ h, int ldh, int I,
                                                                int K) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wave;
-  const int nc = min(n, I - 1);
-  const fp4x2_t* wr[2] = {W + (size_t)nc * ldw, W + (size_t)(I + nc) * ldw};       // gate row n, up row n
-  const e8m0_t* sr[2] = {S + (size_t)nc * (K >> 5), S + (size_t)(I + nc) * (K >> 5)};
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  W4Pre<2, PRE> pre;
-  preload_w4<2, PRE>(wr, sr, 0, K, pre);
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  if (n >= I) return;
-  float acc[NB][2];
-  wave_dots4_b<NB, 2, PRE>(wr, sr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const float g = rbf(acc[b][0]), u = rbf(acc[b][1]);
-      h[(size_t)b * ldh + n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
-    }
-  }
+  decb_gate_up_body<WFp4, NB, PRE, XC>(lanes, x, ldx, ln_w, eps, W, ldw, S, h, ldh, I, K);
 }
 
 // ---------------------------------------------------------------- residual GEMVs (o_proj, down_proj)
@@ -285,9 +222,7 @@ __global__ __launch_bounds__(256) void decb_gemv_fp4_kernel(const svlm_lane* __r
   float s = partial[wave][eb][er];
 #pragma unroll
   for (int p = 1; p < KW; ++p) s += partial[wave + p][eb][er];
-  float v = rbf(s + 0.f);                              // (the single-row kernel's "+ no bias": -0 becomes +0 there too)
-  v = rbf(v + bf2f(epi_raw));
-  y[(size_t)eb * ldy + n] = f2bf(v);
+  y[(size_t)eb * ldy + n] = resid_tail(s, epi_raw);
 }
 
 // ================================================================ launchers
@@ -306,21 +241,8 @@ static inline bool decb4_ok(int B, int K, int ldx, int ldw) { return decb4_k_ok(
     else if ((K) <= 4096) KERNEL<NB, 2, 2> __VA_ARGS__;                     \
     else KERNEL<NB, 2, 4> __VA_ARGS__;                                      \
   } while (0)
-#define DECB4_DISPATCH(KERNEL, B, K, ...)                                   \
-  do {                                                                      \
-    if ((B) == 1) DECB4_K(KERNEL, 1, K, __VA_ARGS__);                       \
-    else if ((B) == 2) DECB4_K(KERNEL, 2, K, __VA_ARGS__);                  \
-    else if ((B) == 3) DECB4_K(KERNEL, 3, K, __VA_ARGS__);                  \
-    else DECB4_K(KERNEL, 4, K, __VA_ARGS__);                                \
-  } while (0)
-// P12 / P34: PRE of the one- and two-lane and of the three- and four-lane instantiations
-#define DECB4_GEMV(B, ROWS, KW, P12, P34, ...)                              \
-  do {                                                                      \
-    if ((B) == 1) decb_gemv_fp4_kernel<1, ROWS, KW, P12> __VA_ARGS__;       \
-    else if ((B) == 2) decb_gemv_fp4_kernel<2, ROWS, KW, P12> __VA_ARGS__;  \
-    else if ((B) == 3) decb_gemv_fp4_kernel<3, ROWS, KW, P34> __VA_ARGS__;  \
-    else decb_gemv_fp4_kernel<4, ROWS, KW, P34> __VA_ARGS__;                \
-  } while (0)
+// the residual GEMV with PRE = P12 at one and two lanes, P34 at three and four
+#define DECB4_GEMV(B, ROWS, KW, P12, P34, ...) DECB_SWITCH_NB(B, decb_gemv_fp4_kernel<NB, ROWS, KW, (NB <= 2 ? P12 : P34)> __VA_ARGS__)
 
 extern "C" int svlm_decb_qkv_fp4(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W4, int ldw,
                                  const void* w_scale, const void* bias, void* q_out, int ldq, int layer, int K, int qd, int kd, int D,
@@ -328,12 +250,11 @@ extern "C" int svlm_decb_qkv_fp4(const void* lanes, int B, const void* x, int ld
   SVLM_CHECK_ARG(lanes != nullptr && decb4_ok(B, K, ldx, ldw) && w_scale != nullptr,
                  "svlm_decb_qkv_fp4: bad B=%d K=%d ldx=%d ldw=%d (B 1..4, K a multiple of 32, ldw >= K / 2 a multiple of 16, B*K*2 <= 64 KB - 256) or no scales",
                  B, K, ldx, ldw);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D == 128 && kd % D == 0 && bias != nullptr && ldq >= qd && layer >= 0,
-                 "svlm_decb_qkv_fp4: bad qd=%d kd=%d D=%d ldq=%d layer=%d (head_dim 128)", qd, kd, D, ldq, layer);
+  if (!decb_qkv_args_ok("svlm_decb_qkv_fp4", qd, kd, D, bias, ldq, layer)) return SVLM_EINVAL;
   const int N = qd + 2 * kd;
-  DECB4_DISPATCH(decb_qkv_fp4_kernel, B, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB4_K(decb_qkv_fp4_kernel, NB, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp4x2_t*)W4, ldw, (const e8m0_t*)w_scale,
-      (const bf16_t*)bias, (bf16_t*)q_out, ldq, layer, N, K, qd, kd, D));
+      (const bf16_t*)bias, (bf16_t*)q_out, ldq, layer, N, K, qd, kd, D)));
   return svlm_check_launch("svlm_decb_qkv_fp4");
 }
 
@@ -341,9 +262,9 @@ extern "C" int svlm_decb_gate_up_fp4(const void* lanes, int B, const void* x, in
                                      const void* w_scale, void* h, int ldh, int I, int K, void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && decb4_ok(B, K, ldx, ldw) && w_scale != nullptr && I > 0 && ldh >= I,
                  "svlm_decb_gate_up_fp4: bad B=%d I=%d K=%d ldx=%d ldw=%d ldh=%d or no scales", B, I, K, ldx, ldw, ldh);
-  DECB4_DISPATCH(decb_gate_up_fp4_kernel, B, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB4_K(decb_gate_up_fp4_kernel, NB, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp4x2_t*)W4, ldw, (const e8m0_t*)w_scale, (bf16_t*)h,
-      ldh, I, K));
+      ldh, I, K)));
   return svlm_check_launch("svlm_decb_gate_up_fp4");
 }
 

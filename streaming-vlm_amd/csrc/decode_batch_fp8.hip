@@ -1,6 +1,7 @@
 // Lane-batched decode-step kernels on OCP e4m3 weights with one power-of-two scale per output row: stream groups (stream_group.py)
-// on an `llm_fp8` engine.  Each kernel is the lane-batched twin of one single-row fp8 kernel (decode_fp8.hip), the relationship
-// decode_batch.hip has to decode_fused.hip / gemv.hip:
+// on an `llm_fp8` engine.  The fused kernels are the lane-batched shells of dec_shell.h over the policy WFp8 (dec_fp8.h) around this
+// file's K loop (cvt16, fma_batch8_b, wave_dots8_b), with the epilogue pieces of the single-row kernels (dec_epi.h); the lm_head and the
+// residual GEMV keep bodies of their own (on the shared ones some instantiations took up to 26 more VGPRs).  Entry, its single-row counterpart:
 //
 //   svlm_decb_qkv_fp8      svlm_dec_qkv_fp8       RMSNorm + QKV + bias + KV append to each lane's own pool slot / linear planes
 //   svlm_decb_gate_up_fp8  svlm_dec_gate_up_fp8   RMSNorm + gate/up + SwiGLU
@@ -26,6 +27,8 @@
 #include "dec_xrow.h"
 #include "dec_fp8.h"
 #include "dec_lanes.h"
+#include "dec_launch.h"           // host side: lane-count switch, qkv argument checks
+#include "dec_shell.h"            // the kernel shells over WFp8 (dec_fp8.h); epilogue pieces: dec_epi.h
 
 // the 16 codes of one 16-B weight vector as fp32, in element order (the factors dot16 feeds its FMAs with)
 __device__ __forceinline__ void cvt16(const u32x4_t& w, float (&wf)[16]) {
@@ -91,48 +94,7 @@ __global__ __launch_bounds__(256) void decb_qkv_fp8_kernel(const svlm_lane* __re
                                                            const float* __restrict__ w_scale, const bf16_t* __restrict__ bias,
                                                            bf16_t* __restrict__ q_out, int ldq, int layer, int N, int K, int qd, int kd,
                                                            int D) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wave;
-  const fp8_t* wr[1] = {W + (size_t)min(n, N - 1) * ldw};
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  W8Pre<1, PRE> pre;
-  preload_w8<1, PRE>(wr, 0, K, pre);
-  const bf16_t bpre = bias[min(n, N - 1)];
-  const float spre = w_scale[min(n, N - 1)];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  if (n >= N) return;
-  float acc[NB][1];
-  wave_dots8_b<NB, 1, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-    const int Hkv = kd / D;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const svlm_lane& L = lanes[b];
-      const bf16_t v = f2bf(acc[b][0] * spre + bf2f(bpre));
-      if (n < qd) {
-        q_out[(size_t)b * ldq + n] = v;
-      } else {
-        const int row = L.state[0];
-        const int slot = L.slot_of[row];
-        const int j = n - qd;
-        const int jj = j < kd ? j : j - kd;
-        const int h = jj / D, d = jj % D;
-        bf16_t* plane = L.pool + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.n_slots * D;
-        plane[((size_t)h * L.n_slots + slot) * D + d] = v;
-        if (L.lin != nullptr) {      // the linear planes' layout of svlm_dec_qkv_lin, at logical row `row`
-          bf16_t* lp = L.lin + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.lin_rows * D;
-          if (j < kd) lp[((size_t)h * (L.lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-          else lp[((size_t)h * L.lin_rows + row) * D + d] = v;
-        }
-      }
-    }
-  }
+  decb_qkv_body<WFp8, NB, PRE, XC>(lanes, x, ldx, ln_w, eps, W, ldw, w_scale, bias, q_out, ldq, layer, N, K, qd, kd, D);
 }
 
 // ---------------------------------------------------------------- gate/up + SwiGLU
@@ -141,37 +103,14 @@ __global__ __launch_bounds__(256) void decb_gate_up_fp8_kernel(const svlm_lane* 
                                                                const bf16_t* __restrict__ ln_w, float eps, const fp8_t* __restrict__ W,
                                                                int ldw, const float* __restrict__ w_scale, bf16_t* __restrict__ h, int ldh,
                                                                int I, int K) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wave;
-  const int nc = min(n, I - 1);
-  const fp8_t* wr[2] = {W + (size_t)nc * ldw, W + (size_t)(I + nc) * ldw};       // gate row n, up row n
-  XRow<XC> xr[NB];
-  bool live[NB];
-  load_rows<NB, XC>(lanes, x, ldx, ln_w, K, xr, live);
-  __builtin_amdgcn_sched_barrier(0);
-  W8Pre<2, PRE> pre;
-  preload_w8<2, PRE>(wr, 0, K, pre);
-  const float sg = w_scale[nc], su = w_scale[I + nc];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_rows<NB, XC>(xr, live, eps, K, xs);
-  if (n >= I) return;
-  float acc[NB][2];
-  wave_dots8_b<NB, 2, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (!live[b]) continue;
-      const float g = rbf(acc[b][0] * sg), u = rbf(acc[b][1] * su);
-      h[(size_t)b * ldh + n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
-    }
-  }
+  decb_gate_up_body<WFp8, NB, PRE, XC>(lanes, x, ldx, ln_w, eps, W, ldw, w_scale, h, ldh, I, K);
 }
 
 // ---------------------------------------------------------------- lm_head + penalty + argmax candidates
 #define DECB_LM8_ROWS 2           // = LM8_ROWS of decode_fp8.hip = DECB_LM_ROWS of decode_batch.hip: one candidate per 8 vocabulary rows
-// SMP: as decb_lm_head_body (decode_batch.hip) -- a live lane in Gumbel mode gets score * inv_temp + noise as its candidate score, the
-// expression of dec_lm_head_fp8_kernel (decode_fp8.hip).
+// The e4m3 head keeps a shell of its own, with the epilogue pieces of dec_epi.h: on decb_lm_head_body (dec_shell.h) over WFp8 its
+// K <= 1024 forms took more registers (<2, 1, 1> 86 -> 91 VGPRs, <3, 1, 1> 87 -> 110) and the three-lane one ran 9 % slower.
+// SMP: a live lane in Gumbel mode gets score * inv_temp + noise as its candidate score (cand_score).
 template <int NB, int PRE, int XC, bool SMP>
 __device__ __forceinline__ void decb_lm_head_fp8_body(const svlm_lane* __restrict__ lanes, const svlm_lane_sample* __restrict__ samples,
                                                       const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ ln_w, float eps,
@@ -218,30 +157,15 @@ __device__ __forceinline__ void decb_lm_head_fp8_body(const svlm_lane* __restric
         if (n >= V) break;
         float v = rbf(acc[b][r] * spre[r]);
         if (lane == 0) logits[(size_t)b * ldl + n] = v;
-        if (L.seen && L.seen[n]) v = v < 0.f ? v * L.penalty : v / L.penalty;
-        for (int s = 0; s < L.n_suppress; ++s)
-          if (suppress[s] == n) v = -INFINITY;
-        if constexpr (SMP) {
-          if (rng) v = v * inv_temp + svlm_gumbel_noise(rng, (unsigned)(L.state[1] + 1), (unsigned)n);
-        }
-        if (v > best[b] || (v == best[b] && n < bi[b])) { best[b] = v; bi[b] = n; }
+        v = cand_score(v, n, L.seen, L.penalty, suppress, L.n_suppress, rng, inv_temp, L.state);
+        cand_take(best[b], bi[b], v, n);
       }
     }
   }
-  __shared__ float sb[NB][4];
-  __shared__ int si[NB][4];
-  if (lane == 0) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) { sb[b][wave] = best[b]; si[b][wave] = bi[b]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < NB && lane_live(lanes[threadIdx.x])) {
-    const int b = threadIdx.x;
-    float bb = sb[b][0];
-    int ii = si[b][0];
-    for (int w = 1; w < 4; ++w)
-      if (sb[b][w] > bb || (sb[b][w] == bb && si[b][w] < ii)) { bb = sb[b][w]; ii = si[b][w]; }
-    float* pv = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (size_t)b * ws_stride);
+  float bb;
+  int ii;
+  if (cand_reduce<NB>(best, bi, bb, ii) && lane_live(lanes[threadIdx.x])) {
+    float* pv = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (size_t)threadIdx.x * ws_stride);
     int* pi = reinterpret_cast<int*>(pv + gridDim.x);
     pv[blockIdx.x] = bb;
     pi[blockIdx.x] = ii;
@@ -348,9 +272,7 @@ __global__ __launch_bounds__(256) void decb_gemv_fp8_kernel(const svlm_lane* __r
   float s = partial[wave][eb][er];
 #pragma unroll
   for (int p = 1; p < KW; ++p) s += partial[wave + p][eb][er];
-  float v = rbf(s * spre + 0.f);                       // (the single-row kernel's "+ no bias": -0 becomes +0 there too)
-  v = rbf(v + bf2f(epi_raw));
-  y[(size_t)eb * ldy + n] = f2bf(v);
+  y[(size_t)eb * ldy + n] = resid_tail(s * spre, epi_raw);
 }
 
 // ================================================================ launchers
@@ -368,32 +290,16 @@ static inline bool decb8_ok(int B, int K, int ldx, int ldw) {
     else if ((K) <= 4096) KERNEL<NB, 4, 2> __VA_ARGS__;                     \
     else KERNEL<NB, 4, 4> __VA_ARGS__;                                      \
   } while (0)
-#define DECB8_DISPATCH(KERNEL, B, K, ...)                                   \
-  do {                                                                      \
-    if ((B) == 1) DECB8_K(KERNEL, 1, K, __VA_ARGS__);                       \
-    else if ((B) == 2) DECB8_K(KERNEL, 2, K, __VA_ARGS__);                  \
-    else if ((B) == 3) DECB8_K(KERNEL, 3, K, __VA_ARGS__);                  \
-    else DECB8_K(KERNEL, 4, K, __VA_ARGS__);                                \
-  } while (0)
-#define DECB8_GEMV(B, ROWS, KW, PRE, ...)                                   \
-  do {                                                                      \
-    if ((B) == 1) decb_gemv_fp8_kernel<1, ROWS, KW, PRE> __VA_ARGS__;       \
-    else if ((B) == 2) decb_gemv_fp8_kernel<2, ROWS, KW, PRE> __VA_ARGS__;  \
-    else if ((B) == 3) decb_gemv_fp8_kernel<3, ROWS, KW, PRE> __VA_ARGS__;  \
-    else decb_gemv_fp8_kernel<4, ROWS, KW, PRE> __VA_ARGS__;                \
-  } while (0)
-
 extern "C" int svlm_decb_qkv_fp8(const void* lanes, int B, const void* x, int ldx, const void* ln_w, float eps, const void* W8, int ldw,
                                  const float* w_scale, const void* bias, void* q_out, int ldq, int layer, int K, int qd, int kd, int D,
                                  void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && decb8_ok(B, K, ldx, ldw) && w_scale != nullptr,
                  "svlm_decb_qkv_fp8: bad B=%d K=%d ldx=%d ldw=%d (B 1..4, K and ldw multiples of 16, B*K*2 <= 64 KB - 256) or no scales", B, K, ldx, ldw);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D == 128 && kd % D == 0 && bias != nullptr && ldq >= qd && layer >= 0,
-                 "svlm_decb_qkv_fp8: bad qd=%d kd=%d D=%d ldq=%d layer=%d (head_dim 128)", qd, kd, D, ldq, layer);
+  if (!decb_qkv_args_ok("svlm_decb_qkv_fp8", qd, kd, D, bias, ldq, layer)) return SVLM_EINVAL;
   const int N = qd + 2 * kd;
-  DECB8_DISPATCH(decb_qkv_fp8_kernel, B, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB8_K(decb_qkv_fp8_kernel, NB, K, <<<(N + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale, (const bf16_t*)bias,
-      (bf16_t*)q_out, ldq, layer, N, K, qd, kd, D));
+      (bf16_t*)q_out, ldq, layer, N, K, qd, kd, D)));
   return svlm_check_launch("svlm_decb_qkv_fp8");
 }
 
@@ -401,8 +307,8 @@ extern "C" int svlm_decb_gate_up_fp8(const void* lanes, int B, const void* x, in
                                      const float* w_scale, void* h, int ldh, int I, int K, void* stream) {
   SVLM_CHECK_ARG(lanes != nullptr && decb8_ok(B, K, ldx, ldw) && w_scale != nullptr && I > 0 && ldh >= I,
                  "svlm_decb_gate_up_fp8: bad B=%d I=%d K=%d ldx=%d ldw=%d ldh=%d or no scales", B, I, K, ldx, ldw, ldh);
-  DECB8_DISPATCH(decb_gate_up_fp8_kernel, B, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
-      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale, (bf16_t*)h, ldh, I, K));
+  DECB_SWITCH_NB(B, DECB8_K(decb_gate_up_fp8_kernel, NB, K, <<<(I + 3) / 4, 256, B * K * 2, (hipStream_t)stream>>>(
+      (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale, (bf16_t*)h, ldh, I, K)));
   return svlm_check_launch("svlm_decb_gate_up_fp8");
 }
 
@@ -417,19 +323,13 @@ extern "C" int svlm_decb_gemv_fp8(const void* lanes, int B, const void* x, int l
 #define DECB8_GEMV_ARGS (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const fp8_t*)W8, ldw, w_scale, (const bf16_t*)residual, ldr, (bf16_t*)y, ldy, N, K
   // the dispatch of svlm_gemv_fp8, branch for branch (ROWS, KW and the grid; PRE does not enter a row's arithmetic)
   if (N <= 8192 && K >= 4096) {
-    DECB8_GEMV(B, 2, 4, 3, <<<(N + 1) / 2, 256, 0, s>>>(DECB8_GEMV_ARGS));
+    DECB_SWITCH_NB(B, decb_gemv_fp8_kernel<NB, 2, 4, 3><<<(N + 1) / 2, 256, 0, s>>>(DECB8_GEMV_ARGS));
   } else if (N >= 16384) {
-    DECB8_GEMV(B, 4, 1, 2, <<<(N + 15) / 16, 256, 0, s>>>(DECB8_GEMV_ARGS));
+    DECB_SWITCH_NB(B, decb_gemv_fp8_kernel<NB, 4, 1, 2><<<(N + 15) / 16, 256, 0, s>>>(DECB8_GEMV_ARGS));
   } else if (N >= 4096 || (long long)N * K >= (8LL << 20)) {
-    DECB8_GEMV(B, 2, 1, 2, <<<(N + 7) / 8, 256, 0, s>>>(DECB8_GEMV_ARGS));
-  } else if (B == 1) {
-    decb_gemv_fp8_kernel<1, 1, 1, 4><<<(N + 3) / 4, 256, 0, s>>>(DECB8_GEMV_ARGS);
-  } else if (B == 2) {
-    decb_gemv_fp8_kernel<2, 1, 1, 4><<<(N + 3) / 4, 256, 0, s>>>(DECB8_GEMV_ARGS);
-  } else if (B == 3) {   // 3 and 4 lanes: two K-steps in flight instead of four, whose x vectors (PRE x NB x 32 B per thread) cost the occupancy
-    decb_gemv_fp8_kernel<3, 1, 1, 2><<<(N + 3) / 4, 256, 0, s>>>(DECB8_GEMV_ARGS);
-  } else {
-    decb_gemv_fp8_kernel<4, 1, 1, 2><<<(N + 3) / 4, 256, 0, s>>>(DECB8_GEMV_ARGS);
+    DECB_SWITCH_NB(B, decb_gemv_fp8_kernel<NB, 2, 1, 2><<<(N + 7) / 8, 256, 0, s>>>(DECB8_GEMV_ARGS));
+  } else {   // 3 and 4 lanes: two K-steps in flight instead of four, whose x vectors (PRE x NB x 32 B per thread) cost the occupancy
+    DECB_SWITCH_NB(B, decb_gemv_fp8_kernel<NB, 1, 1, (NB <= 2 ? 4 : 2)><<<(N + 3) / 4, 256, 0, s>>>(DECB8_GEMV_ARGS));
   }
 #undef DECB8_GEMV_ARGS
   return svlm_check_launch("svlm_decb_gemv_fp8");
@@ -444,9 +344,9 @@ extern "C" int svlm_decb_lm_head_fp8(const void* lanes, int B, const void* x, in
                  "svlm_decb_lm_head_fp8: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d or no scales", B, V, K, ldx, ldw, ldl);
   SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head_fp8: null logits / workspace");
   const int nb = (V + 4 * DECB_LM8_ROWS - 1) / (4 * DECB_LM8_ROWS);
-  DECB8_DISPATCH(decb_lm_head_fp8_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB8_K(decb_lm_head_fp8_kernel, NB, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale, logits, ldl, suppress,
-      (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K));
+      (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K)));
   return svlm_check_launch("svlm_decb_lm_head_fp8");
 }
 
@@ -457,8 +357,8 @@ extern "C" int svlm_decb_lm_head_sample_fp8(const void* lanes, const void* sampl
                  "svlm_decb_lm_head_sample_fp8: bad B=%d V=%d K=%d ldx=%d ldw=%d ldl=%d or no lane / sample table / scales", B, V, K, ldx, ldw, ldl);
   SVLM_CHECK_ARG(ws != nullptr && logits != nullptr, "svlm_decb_lm_head_sample_fp8: null logits / workspace");
   const int nb = (V + 4 * DECB_LM8_ROWS - 1) / (4 * DECB_LM8_ROWS);
-  DECB8_DISPATCH(decb_lm_head_sample_fp8_kernel, B, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
+  DECB_SWITCH_NB(B, DECB8_K(decb_lm_head_sample_fp8_kernel, NB, K, <<<nb, 256, B * K * 2, (hipStream_t)stream>>>(
       (const svlm_lane*)lanes, (const svlm_lane_sample*)samples, (const bf16_t*)x, ldx, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale,
-      logits, ldl, suppress, (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K));
+      logits, ldl, suppress, (float*)ws, svlm_decb_lm_head_ws_stride(V), V, K)));
   return svlm_check_launch("svlm_decb_lm_head_sample_fp8");
 }

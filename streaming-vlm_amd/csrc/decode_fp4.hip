@@ -1,6 +1,7 @@
 // Decode-step (T = 1) weight-streaming GEMVs on OCP MXFP4 weights: e2m1 codes, two per byte, with one e8m0 power-of-two scale per
-// block of 32 K elements (the opt-in `llm_fp4` engine, weights.py:quantize_blocks_mxfp4).  Each kernel is the twin of an fp8 / bf16
-// one, with the same prologue, epilogue and rounding points:
+// block of 32 K elements (the opt-in `llm_fp4` engine, weights.py:quantize_blocks_mxfp4).  The fused kernels are the SHELLS of the
+// fp8 / bf16 ones (dec_shell.h) over the policy WFp4 (dec_fp4.h) -- one prologue, one epilogue (dec_epi.h), the same rounding points --
+// around this file's K loop (fma_batch4, wave_dots4); the plain GEMV and the dequantisation are this file's own.  Entry, counterparts:
 //
 //   svlm_dec_qkv_fp4        svlm_dec_qkv_fp8      / svlm_dec_qkv_lin   RMSNorm -> QKV + bias -> K/V append (+ linear planes)
 //   svlm_dec_gate_up_fp4    svlm_dec_gate_up_fp8  / svlm_dec_gate_up   RMSNorm -> gate/up -> SwiGLU
@@ -23,6 +24,8 @@
 #include "common.h"
 #include "dec_xrow.h"
 #include "dec_fp4.h"
+#include "dec_launch.h"           // host side: lane-count switch, qkv argument checks
+#include "dec_shell.h"            // the kernel shells over WFp4 (dec_fp4.h); epilogue pieces: dec_epi.h
 
 // ---------------------------------------------------------------- fused decode kernels (x staged in LDS)
 template <int NR, int PRE>
@@ -68,91 +71,15 @@ __global__ __launch_bounds__(256) void dec_qkv_fp4_kernel(const bf16_t* __restri
                                                           const int* __restrict__ slot_of, const int* __restrict__ len_dev, int len_host,
                                                           int N, int K, int qd, int kd, int D, int n_slots, bf16_t* __restrict__ k_lin,
                                                           bf16_t* __restrict__ v_lin, int lin_rows) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const fp4x2_t* wr[ROWS];
-  const e8m0_t* sr[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, N - 1);
-    wr[r] = W + (size_t)n * ldw;
-    sr[r] = S + (size_t)n * (K >> 5);
-  }
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  W4Pre<ROWS, PRE> pre;
-  preload_w4<ROWS, PRE>(wr, sr, 0, K, pre);
-  const int row = len_dev ? *len_dev : len_host;
-  const int slot = slot_of[row];
-  bf16_t bpre[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) bpre[r] = bias[min(n0 + r, N - 1)];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  if (n0 >= N) return;
-  float acc[ROWS];
-  wave_dots4<ROWS, PRE>(wr, sr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-      const bf16_t v = f2bf(acc[r] + bf2f(bpre[r]));
-      if (n < qd) {
-        q_out[n] = v;
-      } else {
-        const int j = n - qd;
-        const int jj = j < kd ? j : j - kd;
-        bf16_t* plane = j < kd ? k_planes : v_planes;
-        plane[((size_t)(jj / D) * n_slots + slot) * D + jj % D] = v;
-        if (k_lin != nullptr) {        // the linear planes' layout of svlm_dec_qkv_lin
-          const int h = jj / D, d = jj % D;
-          if (j < kd) k_lin[((size_t)h * (lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-          else v_lin[((size_t)h * lin_rows + row) * D + d] = v;
-        }
-      }
-    }
-  }
+  dec_qkv_body<WFp4, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, S, bias, q_out, k_planes, v_planes, slot_of, len_dev, len_host, N, K, qd, kd, D, n_slots,
+                                    k_lin, v_lin, lin_rows);
 }
 
 template <int ROWS, int PRE, int XC>
 __global__ __launch_bounds__(256) void dec_gate_up_fp4_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ ln_w, float eps,
                                                               const fp4x2_t* __restrict__ W, int ldw, const e8m0_t* __restrict__ S,
                                                               bf16_t* __restrict__ h, int I, int K) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const fp4x2_t* wr[2 * ROWS];
-  const e8m0_t* sr[2 * ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, I - 1);
-    wr[r] = W + (size_t)n * ldw;               // gate row n
-    wr[ROWS + r] = W + (size_t)(I + n) * ldw;  // up row n
-    sr[r] = S + (size_t)n * (K >> 5);
-    sr[ROWS + r] = S + (size_t)(I + n) * (K >> 5);
-  }
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  W4Pre<2 * ROWS, PRE> pre;
-  preload_w4<2 * ROWS, PRE>(wr, sr, 0, K, pre);
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  if (n0 >= I) return;
-  float acc[2 * ROWS];
-  wave_dots4<2 * ROWS, PRE>(wr, sr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= I) break;
-      const float g = rbf(acc[r]), u = rbf(acc[ROWS + r]);
-      h[n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
-    }
-  }
+  dec_gate_up_body<WFp4, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, S, h, I, K);
 }
 
 // ---------------------------------------------------------------- plain GEMV (x from global), optional K split over the waves
@@ -288,10 +215,9 @@ static inline bool fp4_k_ok(int K, int ldw) { return K > 0 && K % 32 == 0 && ldw
 extern "C" int svlm_dec_qkv_fp4(const void* x, const void* ln_w, float eps, const void* W4, int ldw, const void* w_scale, const void* bias,
                                 void* q_out, void* k_planes, void* v_planes, const int* slot_of, const int* len_dev, int len_host, int K, int qd,
                                 int kd, int D, int n_slots, void* k_lin, void* v_lin, int lin_rows, void* stream) {
-  SVLM_CHECK_ARG((k_lin == nullptr) == (v_lin == nullptr) && (k_lin == nullptr || (D == 128 && lin_rows > 0 && lin_rows % 16 == 0 && (len_dev != nullptr || len_host < lin_rows))),
-                 "svlm_dec_qkv_fp4: k_lin / v_lin come together, head_dim 128, lin_rows=%d a multiple of 16 above the row", lin_rows);
   SVLM_CHECK_ARG(fp4_k_ok(K, ldw) && K <= 8192 && w_scale != nullptr, "svlm_dec_qkv_fp4: bad K=%d (a multiple of 32) ldw=%d or no scales", K, ldw);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D > 0 && kd % D == 0 && n_slots > 0 && bias != nullptr, "svlm_dec_qkv_fp4: bad qd=%d kd=%d D=%d", qd, kd, D);
+  if (!dec_qkv_args_ok("svlm_dec_qkv_fp4", "svlm_dec_qkv_fp4", qd, kd, D, n_slots, bias, k_lin, v_lin, lin_rows, len_dev, len_host))
+    return SVLM_EINVAL;
   const int N = qd + 2 * kd;
   DEC4_DISPATCH(dec_qkv_fp4_kernel, QKV4_ROWS, K, <<<(N + 4 * QKV4_ROWS - 1) / (4 * QKV4_ROWS), 256, K * 2, (hipStream_t)stream>>>(
       (const bf16_t*)x, (const bf16_t*)ln_w, eps, (const fp4x2_t*)W4, ldw, (const e8m0_t*)w_scale, (const bf16_t*)bias, (bf16_t*)q_out,

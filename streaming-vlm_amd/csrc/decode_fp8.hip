@@ -1,6 +1,7 @@
 // Decode-step (T = 1) weight-streaming GEMVs on OCP e4m3 weights with one power-of-two scale per output row (the opt-in
-// `llm_fp8` engine, weights.py:quantize_rows_fp8_pow2).  Each kernel is the twin of a bf16 one, with the same prologue, epilogue
-// and rounding points:
+// `llm_fp8` engine, weights.py:quantize_rows_fp8_pow2).  The fused kernels are the SHELLS of the bf16 ones (dec_shell.h) over the
+// policy WFp8 (dec_fp8.h) -- one prologue, one epilogue (dec_epi.h), the same rounding points -- around this file's K loop (fma_batch8,
+// wave_dots8); the plain GEMV and the dequantisation are this file's own.  Entry, its bf16 counterpart:
 //
 //   svlm_dec_qkv_fp8              svlm_dec_qkv_lin      (decode_fused.hip)  RMSNorm -> QKV + bias -> K/V append (+ linear planes)
 //   svlm_dec_gate_up_fp8          svlm_dec_gate_up      (decode_fused.hip)  RMSNorm -> gate/up -> SwiGLU
@@ -17,7 +18,9 @@
 // subnormals included) feeding the same fp32 FMAs the bf16 path sums with.
 #include "common.h"
 #include "dec_xrow.h"
-#include "dec_fp8.h"              // x16, dot16, W8Pre, preload_w8: shared with decode_batch_fp8.hip
+#include "dec_fp8.h"              // x16, dot16, W8Pre, preload_w8, the policy WFp8: shared with decode_batch_fp8.hip
+#include "dec_launch.h"           // host side: lane-count switch, qkv argument checks
+#include "dec_shell.h"            // the kernel shells over WFp8; epilogue pieces: dec_epi.h
 
 // ---------------------------------------------------------------- fused decode kernels (x staged in LDS)
 template <int NR, int PRE>
@@ -55,94 +58,15 @@ __global__ __launch_bounds__(256) void dec_qkv_fp8_kernel(const bf16_t* __restri
                                                           const int* __restrict__ slot_of, const int* __restrict__ len_dev, int len_host,
                                                           int N, int K, int qd, int kd, int D, int n_slots, bf16_t* __restrict__ k_lin,
                                                           bf16_t* __restrict__ v_lin, int lin_rows) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const fp8_t* wr[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, N - 1) * ldw;
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  W8Pre<ROWS, PRE> pre;
-  preload_w8<ROWS, PRE>(wr, 0, K, pre);
-  const int row = len_dev ? *len_dev : len_host;
-  const int slot = slot_of[row];
-  bf16_t bpre[ROWS];
-  float spre[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    bpre[r] = bias[min(n0 + r, N - 1)];
-    spre[r] = w_scale[min(n0 + r, N - 1)];
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  if (n0 >= N) return;
-  float acc[ROWS];
-  wave_dots8<ROWS, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-      const bf16_t v = f2bf(acc[r] * spre[r] + bf2f(bpre[r]));
-      if (n < qd) {
-        q_out[n] = v;
-      } else {
-        const int j = n - qd;
-        const int jj = j < kd ? j : j - kd;
-        bf16_t* plane = j < kd ? k_planes : v_planes;
-        plane[((size_t)(jj / D) * n_slots + slot) * D + jj % D] = v;
-        if (k_lin != nullptr) {        // the linear planes' layout of svlm_dec_qkv_lin
-          const int h = jj / D, d = jj % D;
-          if (j < kd) k_lin[((size_t)h * (lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-          else v_lin[((size_t)h * lin_rows + row) * D + d] = v;
-        }
-      }
-    }
-  }
+  dec_qkv_body<WFp8, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, w_scale, bias, q_out, k_planes, v_planes, slot_of, len_dev, len_host, N, K, qd, kd, D,
+                                    n_slots, k_lin, v_lin, lin_rows);
 }
 
 template <int ROWS, int PRE, int XC>
 __global__ __launch_bounds__(256) void dec_gate_up_fp8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ ln_w, float eps,
                                                               const fp8_t* __restrict__ W, int ldw, const float* __restrict__ w_scale,
                                                               bf16_t* __restrict__ h, int I, int K) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const fp8_t* wr[2 * ROWS];
-  float spre[2 * ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, I - 1);
-    wr[r] = W + (size_t)n * ldw;               // gate row n
-    wr[ROWS + r] = W + (size_t)(I + n) * ldw;  // up row n
-  }
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  W8Pre<2 * ROWS, PRE> pre;
-  preload_w8<2 * ROWS, PRE>(wr, 0, K, pre);
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, I - 1);
-    spre[r] = w_scale[n];
-    spre[ROWS + r] = w_scale[I + n];
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  if (n0 >= I) return;
-  float acc[2 * ROWS];
-  wave_dots8<2 * ROWS, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= I) break;
-      const float g = rbf(acc[r] * spre[r]), u = rbf(acc[ROWS + r] * spre[ROWS + r]);
-      h[n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
-    }
-  }
+  dec_gate_up_body<WFp8, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, w_scale, h, I, K);
 }
 
 template <int ROWS, int PRE, int XC>
@@ -153,50 +77,8 @@ __global__ __launch_bounds__(256) void dec_lm_head_fp8_kernel(const bf16_t* __re
                                                               float* __restrict__ part_val, int* __restrict__ part_idx, int V, int K,
                                                               float inv_temp, const unsigned* __restrict__ rng,
                                                               const int* __restrict__ state) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const fp8_t* wr[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, V - 1) * ldw;
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  W8Pre<ROWS, PRE> pre;
-  preload_w8<ROWS, PRE>(wr, 0, K, pre);
-  float spre[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) spre[r] = w_scale[min(n0 + r, V - 1)];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  if (n0 < V) {
-    float acc[ROWS];
-    wave_dots8<ROWS, PRE>(wr, xs, K, acc, pre);
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= V) break;
-      float v = rbf(acc[r] * spre[r]);
-      if (lane == 0) logits[n] = v;
-      if (seen && seen[n]) v = v < 0.f ? v * penalty : v / penalty;
-      for (int s = 0; s < n_suppress; ++s)
-        if (suppress[s] == n) v = -INFINITY;
-      if (rng) v = v * inv_temp + svlm_gumbel_noise(rng, (unsigned)(state[1] + 1), (unsigned)n);
-      if (v > best || (v == best && n < bi)) { best = v; bi = n; }
-    }
-  }
-  __shared__ float sb[4];
-  __shared__ int si[4];
-  if (lane == 0) { sb[wave] = best; si[wave] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (sb[w] > best || (sb[w] == best && si[w] < bi)) { best = sb[w]; bi = si[w]; }
-    part_val[blockIdx.x] = best;
-    part_idx[blockIdx.x] = bi;
-  }
+  dec_lm_head_body<WFp8, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, w_scale, logits, seen, penalty, suppress, n_suppress, part_val, part_idx, V, K,
+                                        inv_temp, rng, state);
 }
 
 // ---------------------------------------------------------------- plain GEMV (x from global), optional K split over the waves
@@ -328,10 +210,9 @@ static inline bool fp8_k_ok(int K, int ldw) { return K > 0 && K % 16 == 0 && K <
 extern "C" int svlm_dec_qkv_fp8(const void* x, const void* ln_w, float eps, const void* W8, int ldw, const float* w_scale, const void* bias,
                                 void* q_out, void* k_planes, void* v_planes, const int* slot_of, const int* len_dev, int len_host, int K, int qd,
                                 int kd, int D, int n_slots, void* k_lin, void* v_lin, int lin_rows, void* stream) {
-  SVLM_CHECK_ARG((k_lin == nullptr) == (v_lin == nullptr) && (k_lin == nullptr || (D == 128 && lin_rows > 0 && lin_rows % 16 == 0 && (len_dev != nullptr || len_host < lin_rows))),
-                 "svlm_dec_qkv_fp8: k_lin / v_lin come together, head_dim 128, lin_rows=%d a multiple of 16 above the row", lin_rows);
   SVLM_CHECK_ARG(fp8_k_ok(K, ldw) && w_scale != nullptr, "svlm_dec_qkv_fp8: bad K=%d ldw=%d (multiples of 16) or no scales", K, ldw);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D > 0 && kd % D == 0 && n_slots > 0 && bias != nullptr, "svlm_dec_qkv_fp8: bad qd=%d kd=%d D=%d", qd, kd, D);
+  if (!dec_qkv_args_ok("svlm_dec_qkv_fp8", "svlm_dec_qkv_fp8", qd, kd, D, n_slots, bias, k_lin, v_lin, lin_rows, len_dev, len_host))
+    return SVLM_EINVAL;
   const int N = qd + 2 * kd;
   DEC8_DISPATCH(dec_qkv_fp8_kernel, QKV8_ROWS, K, <<<(N + 4 * QKV8_ROWS - 1) / (4 * QKV8_ROWS), 256, K * 2, (hipStream_t)stream>>>(
       (const bf16_t*)x, (const bf16_t*)ln_w, eps, (const fp8_t*)W8, ldw, w_scale, (const bf16_t*)bias, (bf16_t*)q_out, (bf16_t*)k_planes,

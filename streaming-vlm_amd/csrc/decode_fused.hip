@@ -14,9 +14,15 @@
 //
 // All are HBM-bound weight streams: 16-B loads straight to VGPRs, the normalised activation row is
 // staged once per workgroup in LDS (bf16, rounded exactly where the eager module rounds).
+//
+// This file holds the bf16 K loop (fma_batch, wave_dots), the kernels' names and the launchers.  What surrounds the K loop is the
+// shell of each op in dec_shell.h, shared with the e4m3 (decode_fp8.hip) and MXFP4 (decode_fp4.hip) kernels through a weight-format
+// policy (WBf16, dec_stream.h); the KV append, the candidate scoring and the candidate reduce are in dec_epi.h.
 #include "common.h"
 #include "dec_xrow.h"
 #include "dec_stream.h"
+#include "dec_launch.h"           // host side: lane-count switch, qkv argument checks
+#include "dec_shell.h"            // the kernel shells over WBf16 (dec_stream.h); epilogue pieces: dec_epi.h
 
 template <int NR, int PRE>
 __device__ __forceinline__ void fma_batch(const WPre<NR, PRE>& pre, const bf16_t* xs, int base, int K, float (&acc)[NR]) {
@@ -64,86 +70,15 @@ __global__ __launch_bounds__(256) void dec_qkv_kernel(const bf16_t* __restrict__
                                                       const int* __restrict__ len_dev, int len_host, int N, int K, int qd, int kd,
                                                       int D, int n_slots, bf16_t* __restrict__ k_lin, bf16_t* __restrict__ v_lin,
                                                       int lin_rows) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const bf16_t* wr[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, N - 1) * ldw;
-  // x first, then everything that does not depend on it: head of the weight stream, the slot, the bias
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  WPre<ROWS, PRE> pre;
-  preload_w<ROWS, PRE>(wr, 0, K, pre);
-  const int row = len_dev ? *len_dev : len_host;
-  const int slot = slot_of[row];
-  bf16_t bpre[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) bpre[r] = bias[min(n0 + r, N - 1)];
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  if (n0 >= N) return;
-  float acc[ROWS];
-  wave_dots<ROWS, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-      const bf16_t v = f2bf(acc[r] + bf2f(bpre[r]));
-      if (n < qd) {
-        q_out[n] = v;
-      } else {
-        const int j = n - qd;
-        const int jj = j < kd ? j : j - kd;
-        bf16_t* plane = j < kd ? k_planes : v_planes;
-        plane[((size_t)(jj / D) * n_slots + slot) * D + jj % D] = v;
-        if (k_lin != nullptr) {
-          // ... and into the cache's linear planes at logical row `row` (svlm_decode_attn_lin): the value as it is, the key UN-rotated in
-          // its tile position (rows at or above *lin_state are rotated by the reader) -- the decode attention then needs no slot table
-          const int h = jj / D, d = jj % D;
-          if (j < kd) k_lin[((size_t)h * (lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-          else v_lin[((size_t)h * lin_rows + row) * D + d] = v;
-        }
-      }
-    }
-  }
+  dec_qkv_body<WBf16, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, /* S: none */ nullptr, bias, q_out, k_planes, v_planes, slot_of, len_dev, len_host, N, K, qd, kd, D,
+                                     n_slots, k_lin, v_lin, lin_rows);
 }
 
 // ---------------------------------------------------------------- gate/up + SwiGLU
 template <int ROWS, int PRE, int XC>
 __global__ __launch_bounds__(256) void dec_gate_up_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ ln_w, float eps,
                                                           const bf16_t* __restrict__ W, int ldw, bf16_t* __restrict__ h, int I, int K) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const bf16_t* wr[2 * ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, I - 1);
-    wr[r] = W + (size_t)n * ldw;               // gate row n
-    wr[ROWS + r] = W + (size_t)(I + n) * ldw;  // up row n
-  }
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  WPre<2 * ROWS, PRE> pre;
-  preload_w<2 * ROWS, PRE>(wr, 0, K, pre);
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  if (n0 >= I) return;
-  float acc[2 * ROWS];
-  wave_dots<2 * ROWS, PRE>(wr, xs, K, acc, pre);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= I) break;
-      const float g = rbf(acc[r]), u = rbf(acc[ROWS + r]);
-      h[n] = f2bf(apply_act(g, SVLM_ACT_SILU) * u);
-    }
-  }
+  dec_gate_up_body<WBf16, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, /* S: none */ nullptr, h, I, K);
 }
 
 // ---------------------------------------------------------------- lm_head + penalty + argmax candidates
@@ -155,48 +90,8 @@ __global__ __launch_bounds__(256) void dec_lm_head_kernel(const bf16_t* __restri
                                                           float* __restrict__ part_val, int* __restrict__ part_idx, int V, int K,
                                                           float inv_temp, const unsigned* __restrict__ rng,
                                                           const int* __restrict__ state) {
-  bf16_t* xs = reinterpret_cast<bf16_t*>(dyn_smem);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = (blockIdx.x * 4 + wave) * ROWS;
-  const bf16_t* wr[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) wr[r] = W + (size_t)min(n0 + r, V - 1) * ldw;
-  XRow<XC> xr;
-  load_x<XC>(x, ln_w, K, xr);
-  __builtin_amdgcn_sched_barrier(0);
-  WPre<ROWS, PRE> pre;
-  preload_w<ROWS, PRE>(wr, 0, K, pre);
-  __builtin_amdgcn_sched_barrier(0);
-  stage_x<XC>(xr, eps, K, xs);
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  if (n0 < V) {
-    float acc[ROWS];
-    wave_dots<ROWS, PRE>(wr, xs, K, acc, pre);
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= V) break;
-      float v = rbf(acc[r]);
-      if (lane == 0) logits[n] = v;
-      if (seen && seen[n]) v = v < 0.f ? v * penalty : v / penalty;
-      for (int s = 0; s < n_suppress; ++s)
-        if (suppress[s] == n) v = -INFINITY;
-      // temperature sampling = Gumbel-max over the processed scores (sampling.hip); every lane draws the same noise
-      if (rng) v = v * inv_temp + svlm_gumbel_noise(rng, (unsigned)(state[1] + 1), (unsigned)n);
-      if (v > best || (v == best && n < bi)) { best = v; bi = n; }
-    }
-  }
-  __shared__ float sb[4];
-  __shared__ int si[4];
-  if (lane == 0) { sb[wave] = best; si[wave] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (sb[w] > best || (sb[w] == best && si[w] < bi)) { best = sb[w]; bi = si[w]; }
-    part_val[blockIdx.x] = best;
-    part_idx[blockIdx.x] = bi;
-  }
+  dec_lm_head_body<WBf16, ROWS, PRE, XC>(x, ln_w, eps, W, ldw, /* S: none */ nullptr, logits, seen, penalty, suppress, n_suppress, part_val, part_idx, V, K,
+                                         inv_temp, rng, state);
 }
 
 __global__ __launch_bounds__(1024) void argmax_finish_kernel(const float* __restrict__ part_val, const int* __restrict__ part_idx,
@@ -232,10 +127,9 @@ extern "C" int svlm_dec_qkv(const void* x, const void* ln_w, float eps, const vo
 extern "C" int svlm_dec_qkv_lin(const void* x, const void* ln_w, float eps, const void* W, int ldw, const void* bias, void* q_out,
                                 void* k_planes, void* v_planes, const int* slot_of, const int* len_dev, int len_host, int K, int qd,
                                 int kd, int D, int n_slots, void* k_lin, void* v_lin, int lin_rows, void* stream) {
-  SVLM_CHECK_ARG((k_lin == nullptr) == (v_lin == nullptr) && (k_lin == nullptr || (D == 128 && lin_rows > 0 && lin_rows % 16 == 0 && (len_dev != nullptr || len_host < lin_rows))),
-                 "svlm_dec_qkv_lin: k_lin / v_lin come together, head_dim 128, lin_rows=%d a multiple of 16 above the row", lin_rows);
   SVLM_CHECK_ARG(smem_ok(K) && ldw >= K && ldw % 8 == 0, "svlm_dec_qkv: bad K=%d ldw=%d", K, ldw);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D > 0 && kd % D == 0 && n_slots > 0 && bias != nullptr, "svlm_dec_qkv: bad qd=%d kd=%d D=%d", qd, kd, D);
+  if (!dec_qkv_args_ok("svlm_dec_qkv", "svlm_dec_qkv_lin", qd, kd, D, n_slots, bias, k_lin, v_lin, lin_rows, len_dev, len_host))
+    return SVLM_EINVAL;
   const int N = qd + 2 * kd;
   // one row per wave: two rows per wave were measured on the 7B shape (4608 x 3584) and are slower (9.96 vs 8.8 us)
   DEC_DISPATCH(dec_qkv_kernel, 1, K, <<<(N + 3) / 4, 256, K * 2, (hipStream_t)stream>>>(

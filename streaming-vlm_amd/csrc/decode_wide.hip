@@ -30,12 +30,17 @@
 // LANE INDEPENDENCE.  A column of the MFMA result depends on that column of the B operand alone, and neither the split plan nor a
 // wave's instruction stream depends on B or on which column a lane sits in: a live lane's outputs are a function of its own inputs.
 //
+// EPILOGUES.  The new K / V row goes where every qkv kernel puts it (lane_kv_append, dec_lanes.h -> kv_append, dec_epi.h); the head's
+// candidates are scored and compared by cand_score / cand_take and the residual GEMV ends in resid_tail (dec_epi.h), as in the VALU
+// kernels.  The MFMA loops and the norm prologue are this file's own.
+//
 // Arguments: 1 <= B <= 16; K > 0 and a multiple of 8 (the last block is masked in 8-element chunks); leading dimensions as the
 // svlm_decb_* entries.  The fused entries need K <= 4096 and B * ldxs(K) * 2 <= 120 KB of dynamic LDS (ldxs = the padded row).
 #include "common.h"
 #include "dec_xrow.h"
 #include "dec_stream.h"
-#include "dec_lanes.h"
+#include "dec_launch.h"           // host side: the qkv argument check
+#include "dec_lanes.h"            // the lane table, lane_kv_append; the epilogue pieces shared with the VALU kernels: dec_epi.h
 
 #define DECW_MAX_LANES 16
 #define DECW_PRE 4                      // fused kernels: blocks per weight batch (two batches in registers)
@@ -209,17 +214,8 @@ __global__ __launch_bounds__(256) void decw_qkv_kernel(const svlm_lane* __restri
     const bf16_t v = f2bf(acc[0][e] + bf2f(bias[n]));
     if (n < qd) {
       q_out[(size_t)b * ldq + n] = v;
-    } else {                                   // exactly where decb_qkv_kernel puts the lane's new K / V row
-      const int j = n - qd;
-      const int jj = j < kd ? j : j - kd;
-      const int h = jj / D, d = jj % D;
-      bf16_t* plane = L.pool + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.n_slots * D;
-      plane[((size_t)h * L.n_slots + slot) * D + d] = v;
-      if (L.lin != nullptr) {
-        bf16_t* lp = L.lin + (size_t)(layer * 2 + (j < kd ? 0 : 1)) * Hkv * L.lin_rows * D;
-        if (j < kd) lp[((size_t)h * (L.lin_rows >> 4) + (row >> 4)) * 2048 + (d >> 5) * 512 + (((d >> 3) & 3) * 16 + (row & 15)) * 8 + (d & 7)] = v;
-        else lp[((size_t)h * L.lin_rows + row) * D + d] = v;
-      }
+    } else {
+      lane_kv_append(L, layer, Hkv, D, row, slot, n - qd, kd, v);
     }
   }
 }
@@ -272,15 +268,13 @@ __global__ __launch_bounds__(256) void decw_lm_head_kernel(const svlm_lane* __re
       if (n >= V) break;
       float v = rbf(acc[0][e]);
       logits[(size_t)b * ldl + n] = v;
-      if (L.seen && L.seen[n]) v = v < 0.f ? v * L.penalty : v / L.penalty;
-      for (int s = 0; s < L.n_suppress; ++s)
-        if (suppress[s] == n) v = -INFINITY;
-      if (v > best || (v == best && n < bi)) { best = v; bi = n; }
+      v = cand_score(v, n, L.seen, L.penalty, suppress, L.n_suppress, nullptr, 1.0f, L.state);
+      cand_take(best, bi, v, n);
     }
   }
   const float ob = __shfl_down(best, 16, 64);            // the other half of the candidate group (rows 4 higher)
   const int oi = __shfl_down(bi, 16, 64);
-  if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  cand_take(best, bi, ob, oi);
   const int part = blockIdx.x * 2 + (g >> 1);
   if (live && (g & 1) == 0 && part < n_parts) {
     float* pv = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + (size_t)b * ws_stride);
@@ -356,10 +350,7 @@ __global__ __launch_bounds__(KW * 64) void decw_gemv_kernel(const svlm_lane* __r
   for (int e = 0; e < 4; ++e) {
     const int n = n0 + 4 * g + e;
     if (n >= N) break;
-    float v = sum[e] + 0.f;
-    v = rbf(v);
-    v = rbf(v + bf2f(residual[(size_t)r * ldr + n]));
-    y[(size_t)r * ldy + n] = f2bf(v);
+    y[(size_t)r * ldy + n] = resid_tail(sum[e], residual[(size_t)r * ldr + n]);
   }
 }
 
@@ -421,8 +412,7 @@ extern "C" int svlm_decw_qkv(const void* lanes, int B, const void* x, int ldx, c
   SVLM_CHECK_ARG(decw_lanes_ok(lanes, B) && decw_fused_ok(B, K, ldx) && ldw >= K && ldw % 8 == 0,
                  "svlm_decw_qkv: bad B=%d K=%d ldx=%d ldw=%d (1..16 lanes, K a multiple of 8 up to 4096, the staged rows within %d B of LDS)", B, K,
                  ldx, ldw, DECW_LDS_DYN_MAX);
-  SVLM_CHECK_ARG(qd > 0 && kd > 0 && D == 128 && kd % D == 0 && bias != nullptr && ldq >= qd && layer >= 0,
-                 "svlm_decw_qkv: bad qd=%d kd=%d D=%d ldq=%d layer=%d (head_dim 128)", qd, kd, D, ldq, layer);
+  if (!decb_qkv_args_ok("svlm_decw_qkv", qd, kd, D, bias, ldq, layer)) return SVLM_EINVAL;
   const int N = qd + 2 * kd, dyn = B * decw_ldxs(K) * 2;
   if (dyn > 65536 && svlm_decw_reserve_lds() != SVLM_OK) return SVLM_ELAUNCH;
   DECW_XC(decw_qkv_kernel, K, <<<(N + 15) / 16, 256, dyn, (hipStream_t)stream>>>(
